@@ -14,7 +14,9 @@ Domain:  --scaling strong (the default at N > 1): the global domain is --nx x --
          --scaling weak: every GPU owns --nx x --ny columns (256 x 256 x 64 per GPU);
          --global-nx / --global-ny: an explicit global domain, e.g. config 3 = `--gpus 8 --global-nx 512 --global-ny 512`
          (2 x 4 ranks of 256 x 128 columns).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline; --full adds what
+takes runs of its own: the reported-only legs, the tight and warm-start solves, the kernel rooflines with the bandwidth probe
+and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -73,7 +75,16 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="edge of the CPU-baseline sample domain (columns); 0 = 256 with >= 16 threads, else 112")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads (= subdomains) of the CPU baseline; 0 = usable cores (affinity, cgroup quota), at most 128")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: no_hint / no_sharing / all_fp64 / heterogeneous legs, tight and "
+                         "warm-start solves, kernel rooflines and bandwidth probe, CPU baseline (the options above that tune "
+                         "these only act with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -310,6 +321,8 @@ def main():
     cells_total = Nx * Ny * Nz
     value = cells_total * args.steps / dt
     info = infos[-1]
+    if args.dump_outputs:   # before anything below solves into x again
+        dump_outputs(args.dump_outputs, x, info, rank, world)
     # SURVEY 8(d) also asks for a tight run (rtol 1e-8, atol 1e-30 as in tests/test_pprts_symmetry/tenstream.options) and
     # a warm start (previous solution as initial guess, default tolerances): reported in `config`, never part of `value`
     spread = dict(timed_steps.last)
@@ -317,48 +330,50 @@ def main():
     # (check_every = 0, krylov_run): one synchronisation per solve.  Reported beside it: the same steps with the hint off
     # (check_every fixed at 2, the library's non-adaptive cadence: a look every second iteration) -- never part of `value`
     no_hint = None
-    if args.check_every is None and not args.explicit and world == 1:
+    if args.full and args.check_every is None and not args.explicit and world == 1:
         dt_nh, infos_nh, failed_nh = timed_steps(check_every=2)
         if failed_nh is None:
             no_hint = {"cells_per_s": cells_total * args.steps / dt_nh, "ms_per_step": dt_nh / args.steps * 1e3,
                        "iterations": infos_nh[-1].niter, "step_ms_min_med_max": timed_steps.last["step_ms_min_med_max"],
                        "how": "check_every = 2: no iteration-count hint, the host looks at the flag every second iteration"}
-    x.zero_()
-    tight = s.solve(b, x, rtol=1e-8, atol=1e-30, **kw)
-    warm = s.solve(b, x, **kw)
+    if args.full:
+        x.zero_()
+        tight = s.solve(b, x, rtol=1e-8, atol=1e-30, **kw)
+        warm = s.solve(b, x, **kw)
 
-    # ---- rooflines, HIP events on the solver's stream (tsx_bench_kernel): the operator apply, one whole iteration, and
-    # the preconditioner (one application = pc_sweeps + 1 half-grid passes; one intermediate pass of the scan kernels)
-    spmv_ms = s.bench_kernel(0, args.kernel_reps)
-    iter_ms = s.bench_kernel(1, max(4, args.kernel_reps // 4))
-    bytes_spmv = s.algorithmic_bytes(0)
-    bytes_iter = s.algorithmic_bytes(1)
-    pc_ms = pass_ms = None
+        # ---- rooflines, HIP events on the solver's stream (tsx_bench_kernel): the operator apply, one whole iteration, and
+        # the preconditioner (one application = pc_sweeps + 1 half-grid passes; one intermediate pass of the scan kernels)
+        spmv_ms = s.bench_kernel(0, args.kernel_reps)
+        iter_ms = s.bench_kernel(1, max(4, args.kernel_reps // 4))
+        bytes_spmv = s.algorithmic_bytes(0)
+        bytes_iter = s.algorithmic_bytes(1)
     dd_on, dd_nent = s.dedup_info()
     pc_shared = dd_on or bool(getattr(s, "dedup_mode", 0) & 2)   # the preconditioner reads per-block records through an index
     pc_ran, sweeps, scan, rec_shared = s.pc_info()   # what the solves above actually ran (automatic pass count, zebra on odd grids)
+    pc_ms = pass_ms = None
     flow = flow_ms = bytes_flow = None
-    if scan and args.pc_sweeps == 0:
-        pc_ms = s.bench_kernel(2, args.kernel_reps)
-        pass_ms = s.bench_kernel(3, 4 * args.kernel_reps)
-        flow = s.flow_info()   # of the application just timed: do the intermediate passes run as one launch (tsx_k_pcs_flow)?
-        if flow["in_use"]:
-            try:
-                flow_ms = s.bench_kernel(4, args.kernel_reps)
-                flow = s.flow_info()   # (as the Krylov loop issues it: from pass 1)
-                bytes_flow = s.algorithmic_bytes(4)
-            except Exception:   # several ranks: the launch holds the rank faces and cannot be timed alone (tsx_bench_kernel says so)
-                flow_ms = bytes_flow = None
-    bw = s.probe_bandwidth(1 << 30, 5)   # what plain streaming kernels reach on this box: copy and read-only, best variant each
-    copy_gbps = bw["copy_GBps"]
-    # the byte counts follow the storage format in use: take them while the solver is in the state that was timed
-    bytes_survey_spmv = s.algorithmic_bytes(10)
-    bytes_pass, bytes_pc = (s.algorithmic_bytes(3), s.algorithmic_bytes(2)) if pass_ms is not None else (None, None)
+    if args.full:
+        if scan and args.pc_sweeps == 0:
+            pc_ms = s.bench_kernel(2, args.kernel_reps)
+            pass_ms = s.bench_kernel(3, 4 * args.kernel_reps)
+            flow = s.flow_info()   # of the application just timed: do the intermediate passes run as one launch (tsx_k_pcs_flow)?
+            if flow["in_use"]:
+                try:
+                    flow_ms = s.bench_kernel(4, args.kernel_reps)
+                    flow = s.flow_info()   # (as the Krylov loop issues it: from pass 1)
+                    bytes_flow = s.algorithmic_bytes(4)
+                except Exception:   # several ranks: the launch holds the rank faces and cannot be timed alone (tsx_bench_kernel says so)
+                    flow_ms = bytes_flow = None
+        bw = s.probe_bandwidth(1 << 30, 5)   # what plain streaming kernels reach on this box: copy and read-only, best variant each
+        copy_gbps = bw["copy_GBps"]
+        # the byte counts follow the storage format in use: take them while the solver is in the state that was timed
+        bytes_survey_spmv = s.algorithmic_bytes(10)
+        bytes_pass, bytes_pc = (s.algorithmic_bytes(3), s.algorithmic_bytes(2)) if pass_ms is not None else (None, None)
 
     # ---- second leg, reported under config.no_sharing and never part of `value`: the same solves with every cell's block
     # stored (TSX_DEDUP=0 / TSX_PC_RECSHARE=0: what any field whose cells all differ gets, e.g. --field heterogeneous)
     no_sharing = None
-    if (dd_on or getattr(s, "dedup_mode", 0) & 2) and not args.skip_no_sharing and not args.explicit:
+    if args.full and (dd_on or getattr(s, "dedup_mode", 0) & 2) and not args.skip_no_sharing and not args.explicit:
         keep = {k: os.environ.get(k) for k in ("TSX_DEDUP", "TSX_PC_RECSHARE")}
         os.environ["TSX_DEDUP"] = "0"
         os.environ["TSX_PC_RECSHARE"] = "0"
@@ -389,7 +404,7 @@ def main():
     # "everything_fp64": no reduced precision anywhere, the preconditioner on the exact fp64 blocks (fp32_directions = 0,
     # pc_coeff_fp16 = 0) -- the reference's default arithmetic (ireals = real64) end to end
     all_fp64 = None
-    if world == 1 and not args.skip_extra_legs and not args.explicit:   # (one rank: the driver's N = 1 line carries it)
+    if args.full and world == 1 and not args.skip_extra_legs and not args.explicit:   # (one rank: the driver's N = 1 line carries it)
         all_fp64 = {}
         for name, ov in (("recurrence_fp64", dict(fp32_directions=1)), ("everything_fp64", dict(fp32_directions=0, pc_coeff_fp16=0))):
             dt_f, infos_f, failed_f = timed_steps(**ov)
@@ -412,7 +427,7 @@ def main():
     # so no two cells share a transport block (what an LES humidity / aerosol field + gas optics delivers); same generator
     # seed, same solves.  The operator reads every cell's own block, the preconditioner groups near-identical ones
     heterogeneous = None
-    if world == 1 and args.field == "clouds" and not args.skip_extra_legs and not args.explicit:
+    if args.full and world == 1 and args.field == "clouds" and not args.skip_extra_legs and not args.explicit:
         (ka_h, ks_h, g_h), b_h = make_field("heterogeneous")
         opt_h = (dev_f(ka_h), dev_f(ks_h), dev_f(g_h)) + optprop[3:]
         s.set_optprop(*opt_h)
@@ -465,38 +480,6 @@ def main():
 
     out = None
     if rank == 0:
-        r_spmv = roof("tsx_k_spmv_w (y = (I - T) x, fp64 x and y)", spmv_ms, bytes_spmv,
-                      ["tsx_k_spmv", (",0,1,double,double", ",0,2,double,double"), ",true,double>" if dd_on else ",false,double>"],
-                      bytes_survey_spmv)
-        r_iter = roof("one BiCGStab iteration (2 M^-1, 2 SpMV, 3 vector updates)", iter_ms, bytes_iter, None)
-        if not dd_on:   # the committed PMC profile is of the shared-block kernels
-            r_iter["traffic"] = r_iter["traffic_GBps"] = r_iter["traffic_source"] = None
-        r_iter["basis"] = ("SURVEY 8(d)'s 2*B_spmv + 16*N*sv: the reference's iteration without M^-1, every cell's block "
-                           "stored; this iteration also runs M^-1 twice and shares identical blocks, see `traffic`")
-        r_pass = None
-        if pass_ms is not None:
-            kname = "tsx_k_pcs_rb" if solver == "3_10" else "tsx_k_pcsh_rb"
-            r_pass = roof(f"{kname}<..., GS, MODE 0, RQ 2> (one intermediate red-black pass of M^-1)", pass_ms,
-                          bytes_pass, [kname, (",true,0,true,2,", ",true,0,true,2>") if pc_shared else (",true,0,false,2,", ",true,0,false,2>")])
-        r_pc = None
-        if pc_ms is not None:
-            r_pc = {"kernel": f"M^-1: {sweeps + 1} half-grid passes", "ms_per_application": pc_ms,
-                    "bytes_per_application": bytes_pc,
-                    "achieved": bytes_pc / (pc_ms * 1e-3) / 1e9, "unit": "GB/s"}
-        # the kernel the solve spends most of its time in: the preconditioner pass (about half of an iteration) when the
-        # scan kernels run, else the operator apply
-        dominant = r_pass if r_pass is not None else r_spmv
-        r_flow = None
-        if flow_ms is not None:
-            # the intermediate passes of an application run as ONE launch: that launch is where the solve spends its time
-            npass = flow["end_pass"] - flow["first_pass"]
-            r_flow = roof(f"tsx_k_pcs_flow (passes {flow['first_pass']}..{flow['end_pass'] - 1} of one M^-1 application in one launch: "
-                          f"{npass} intermediate red-black passes, work items (pass, tile) behind a ticket counter)", flow_ms,
-                          bytes_flow, ["tsx_k_pcs_flow"])
-            r_flow["passes_per_launch"] = npass
-            r_flow["us_per_pass"] = flow_ms * 1e3 / npass
-            r_flow["the_same_pass_as_its_own_launch_us"] = pass_ms * 1e3
-            dominant = r_flow
         out = {
             "metric": f"pprts {solver} diffuse-solve cells/s" + (" (explicit solver)" if args.explicit else ""),
             "value": value,
@@ -539,30 +522,61 @@ def main():
                 "solve_ms_device": info.solve_ms,
                 "import_ms": info.import_ms,
                 "export_ms": info.export_ms,
-                "iter_ms": iter_ms,
                 "first_solve": spread["first_solve"],
                 "step_ms_min_med_max": spread["step_ms_min_med_max"],
-                "no_hint": no_hint,
-                "flow_kernel": flow,
-                "tight_run": {"rtol": 1e-8, "iterations": tight.niter, "reason": tight.reason, "solve_ms": tight.solve_ms},
-                "warm_start": {"iterations": warm.niter, "reason": warm.reason, "solve_ms": warm.solve_ms},
-                "iter_GBps": bytes_iter / (iter_ms * 1e-3) / 1e9,
-                "copy_GBps_measured": copy_gbps,
-                "read_GBps_measured": bw["read_GBps"],
-                "bandwidth_probe": dict(bw, note="best of 1 / 4 / 8 sixteen-byte accesses per lane in flight, plain and "
-                                                 "non-temporal, grids of 2048 / 4096 / 16384 workgroups, 1 GiB"),
                 "field": args.field,
-                "no_sharing": no_sharing,
-                "all_fp64": all_fp64,
-                "heterogeneous": heterogeneous,
                 "baseline_config": baseline_config(solver, Nx, Ny, Nz, world, npx, npy, scaling),
             },
-            "roofline": dominant,
-            "roofline_pass": r_pass,
-            "roofline_spmv": r_spmv,
-            "roofline_iter": r_iter,
-            "roofline_pc": r_pc,
         }
+    if rank == 0 and args.full:
+        r_spmv = roof("tsx_k_spmv_w (y = (I - T) x, fp64 x and y)", spmv_ms, bytes_spmv,
+                      ["tsx_k_spmv", (",0,1,double,double", ",0,2,double,double"), ",true,double>" if dd_on else ",false,double>"],
+                      bytes_survey_spmv)
+        r_iter = roof("one BiCGStab iteration (2 M^-1, 2 SpMV, 3 vector updates)", iter_ms, bytes_iter, None)
+        if not dd_on:   # the committed PMC profile is of the shared-block kernels
+            r_iter["traffic"] = r_iter["traffic_GBps"] = r_iter["traffic_source"] = None
+        r_iter["basis"] = ("SURVEY 8(d)'s 2*B_spmv + 16*N*sv: the reference's iteration without M^-1, every cell's block "
+                           "stored; this iteration also runs M^-1 twice and shares identical blocks, see `traffic`")
+        r_pass = None
+        if pass_ms is not None:
+            kname = "tsx_k_pcs_rb" if solver == "3_10" else "tsx_k_pcsh_rb"
+            r_pass = roof(f"{kname}<..., GS, MODE 0, RQ 2> (one intermediate red-black pass of M^-1)", pass_ms,
+                          bytes_pass, [kname, (",true,0,true,2,", ",true,0,true,2>") if pc_shared else (",true,0,false,2,", ",true,0,false,2>")])
+        r_pc = None
+        if pc_ms is not None:
+            r_pc = {"kernel": f"M^-1: {sweeps + 1} half-grid passes", "ms_per_application": pc_ms,
+                    "bytes_per_application": bytes_pc,
+                    "achieved": bytes_pc / (pc_ms * 1e-3) / 1e9, "unit": "GB/s"}
+        # the kernel the solve spends most of its time in: the preconditioner pass (about half of an iteration) when the
+        # scan kernels run, else the operator apply
+        dominant = r_pass if r_pass is not None else r_spmv
+        r_flow = None
+        if flow_ms is not None:
+            # the intermediate passes of an application run as ONE launch: that launch is where the solve spends its time
+            npass = flow["end_pass"] - flow["first_pass"]
+            r_flow = roof(f"tsx_k_pcs_flow (passes {flow['first_pass']}..{flow['end_pass'] - 1} of one M^-1 application in one launch: "
+                          f"{npass} intermediate red-black passes, work items (pass, tile) behind a ticket counter)", flow_ms,
+                          bytes_flow, ["tsx_k_pcs_flow"])
+            r_flow["passes_per_launch"] = npass
+            r_flow["us_per_pass"] = flow_ms * 1e3 / npass
+            r_flow["the_same_pass_as_its_own_launch_us"] = pass_ms * 1e3
+            dominant = r_flow
+        out["config"].update({
+            "iter_ms": iter_ms,
+            "no_hint": no_hint,
+            "flow_kernel": flow,
+            "tight_run": {"rtol": 1e-8, "iterations": tight.niter, "reason": tight.reason, "solve_ms": tight.solve_ms},
+            "warm_start": {"iterations": warm.niter, "reason": warm.reason, "solve_ms": warm.solve_ms},
+            "iter_GBps": bytes_iter / (iter_ms * 1e-3) / 1e9,
+            "copy_GBps_measured": copy_gbps,
+            "read_GBps_measured": bw["read_GBps"],
+            "bandwidth_probe": dict(bw, note="best of 1 / 4 / 8 sixteen-byte accesses per lane in flight, plain and "
+                                             "non-temporal, grids of 2048 / 4096 / 16384 workgroups, 1 GiB"),
+            "no_sharing": no_sharing,
+            "all_fp64": all_fp64,
+            "heterogeneous": heterogeneous,
+        })
+        out.update(roofline=dominant, roofline_pass=r_pass, roofline_spmv=r_spmv, roofline_iter=r_iter, roofline_pc=r_pc)
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, solver, dx, dz, albedo, s, b, x, Nx, Ny, kw)
     if world > 1:
@@ -570,6 +584,31 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out))
+
+
+DUMP_SAMPLE = 4 << 20   # entries of x written at most, over all ranks (fp64: 32 MiB)
+
+
+def dump_outputs(path, x, info, rank, world):
+    """What a caller of the timed path receives from the last timed step, as path/<name>.npy:
+    x (x_rank<r> with several ranks, each its own block): the solution in fp64, in the solver's vector shape when it holds at
+    most DUMP_SAMPLE / world entries, else that many entries of the flattened vector at fixed positions (sorted, drawn with
+    numpy's default_rng(0), so the same for every run of the same arguments); solve_info (rank 0): iterations, reason, |r|,
+    |r0| of that solve, and residual_history (rank 0) its residual norms.  The inputs are generated from fixed seeds, so two
+    builds can be compared file by file."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n, cap = x.numel(), DUMP_SAMPLE // world
+    if n <= cap:
+        xs = x.cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+        xs = x.reshape(-1)[torch.from_numpy(idx).to(x.device)].cpu().numpy()
+    np.save(os.path.join(path, "x.npy" if world == 1 else f"x_rank{rank}.npy"), xs.astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "solve_info.npy"), np.array([info.niter, info.reason, info.rnorm, info.rnorm0], dtype=np.float64))
+        np.save(os.path.join(path, "residual_history.npy"), np.asarray(info.res_hist, dtype=np.float64))
 
 
 def pmc_traffic(solver, size, patterns):

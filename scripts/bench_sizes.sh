@@ -1,8 +1,8 @@
 # usage (GPU box): bash scripts/bench_sizes.sh  -- bench.py's line at the metric domain (all legs) and at 128 x 128 / 64 x 64 (headline leg only), condensed
 O=gpurun_out/r05; mkdir -p $O
-python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_quick_line.json 2> $O/bench_quick_err.log; tail -2 $O/bench_quick_err.log
-python bench.py --no-cpu-baseline --skip-extra-legs --skip-no-sharing --steps 20 --warmup 5 --nx 128 --ny 128 > $O/c2_quick_line.json 2>/dev/null
-python bench.py --no-cpu-baseline --skip-extra-legs --skip-no-sharing --steps 20 --warmup 5 --nx 64 --ny 64 > $O/s64_quick_line.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_quick_line.json 2> $O/bench_quick_err.log; tail -2 $O/bench_quick_err.log
+python bench.py --full --no-cpu-baseline --skip-extra-legs --skip-no-sharing --steps 20 --warmup 5 --nx 128 --ny 128 > $O/c2_quick_line.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --skip-extra-legs --skip-no-sharing --steps 20 --warmup 5 --nx 64 --ny 64 > $O/s64_quick_line.json 2>/dev/null
 python - <<PY
 import json
 for f in ("bench_quick","c2_quick","s64_quick"):

@@ -2,7 +2,7 @@
 # exchange; usage (GPU box): bash scripts/halo_every_study.sh [local nx] [local ny]
 NX=${1:-64}; NY=${2:-64}
 for v in "TSX_PC_HALO=0" "TSX_PC_HALO_EVERY=1" "TSX_PC_HALO_EVERY=2" "TSX_PC_HALO_EVERY=4" "TSX_PC_HALO_EVERY=8"; do
-  env $v python bench.py --gpus 4 --transport host --nx $NX --ny $NY --steps 1 --warmup 1 --no-cpu-baseline --kernel-reps 2 > /tmp/he.json 2>/tmp/he.err
+  env $v python bench.py --full --gpus 4 --transport host --nx $NX --ny $NY --steps 1 --warmup 1 --no-cpu-baseline --kernel-reps 2 > /tmp/he.json 2>/tmp/he.err
   python - "$v" <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--steps", "10", "--warmup", "2"] + sys.argv[1:],
+p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"] + sys.argv[1:],
                    capture_output=True, text=True)
 lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
 if not lines:

@@ -1,7 +1,7 @@
 # solve rate against the domain size on one GPU; usage (GPU box): bash scripts/size_scan.sh
 for sz in "64 64" "128 128" "256 256" "512 512" "1024 512"; do
   set -- $sz
-  python bench.py --no-cpu-baseline --steps 3 --warmup 1 --nx $1 --ny $2 > /tmp/sz.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --nx $1 --ny $2 > /tmp/sz.json 2>/dev/null
   python - $1 $2 <<'PY'
 import json, sys
 d = json.loads(open("/tmp/sz.json").read().strip().splitlines()[-1]); c = d["config"]; r = d["roofline"]

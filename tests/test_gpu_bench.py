@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def _line(p):
 
 
 def test_bench_one_gpu_line_has_the_contract_keys(gpu):
-    out = _line(_run(["--nx", "64", "--ny", "32"] + SMALL))
+    out = _line(_run(["--nx", "64", "--ny", "32", "--full"] + SMALL))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "roofline_spmv", "roofline_iter", "roofline_pc"):
         assert k in out, k
@@ -41,10 +42,35 @@ def test_bench_one_gpu_line_has_the_contract_keys(gpu):
     for k in ("first_solve", "step_ms_min_med_max", "no_hint"):
         assert k in out["config"], k
     # the metric names the solver that ran
-    out8 = _line(_run(["--nx", "16", "--ny", "12", "--solver", "8_16"] + SMALL))
+    out8 = _line(_run(["--nx", "16", "--ny", "12", "--solver", "8_16", "--full"] + SMALL))
     assert out8["metric"].startswith("pprts 8_16") and "tsx_k_pcsh_rb" in out8["roofline"]["kernel"]
     for r in (out["roofline"], out["roofline_pass"], out["roofline_spmv"], out8["roofline"], out8["roofline_spmv"]):
         assert 0 < r["frac"] < 1, r   # bytes of the storage format in use: never above the peak
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """Without --full: the headline keys and nothing measured beside them, --steps timed steps, and --dump-outputs writes what the
+    last timed step computed (fp64, the whole solution at this size); two runs of the same arguments solve the same system."""
+    args = ["--nx", "64", "--ny", "32", "--nz", "16", "--steps", "3", "--warmup", "1"]
+    xs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _line(_run(args + ["--dump-outputs", str(d)]))
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype",
+                    "data", "config"):
+            assert key in out, key
+        assert "roofline" not in out and "cpu_baseline" not in out
+        assert not {"tight_run", "no_hint", "no_sharing", "all_fp64", "heterogeneous"} & set(out["config"])
+        assert out["steps"] == 3 and out["config"]["reason"] in (2, 3)
+        assert out["value"] == pytest.approx(64 * 32 * 16 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+        assert sorted(os.listdir(d)) == ["residual_history.npy", "solve_info.npy", "x.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        info, x = np.load(d / "solve_info.npy"), np.load(d / "x.npy")
+        assert info.dtype == x.dtype == np.float64 and x.shape == (32, 64, 17, 10)
+        assert info[0] == out["config"]["iterations"] and info[1] == out["config"]["reason"]
+        assert np.isfinite(x).all() and np.abs(x).max() > 0
+        xs.append(x)
+    assert np.abs(xs[0] - xs[1]).max() <= 1e-6 * np.abs(xs[0]).max()
 
 
 @pytest.mark.parametrize("extra,glob,local,scaling", [
@@ -71,7 +97,7 @@ def test_bench_eight_ranks_on_the_two_by_four_grid(gpu):
     "256x256x64 at 1/2/4/8 GPU")."""
     clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--global-nx", "64", "--global-ny", "64",
-                        "--transport", "host"] + SMALL, capture_output=True, text=True, timeout=1200, env=clean, cwd=ROOT)
+                        "--transport", "host", "--full"] + SMALL, capture_output=True, text=True, timeout=1200, env=clean, cwd=ROOT)
     out = _line(p)
     assert out["n_gpus"] == 8 and out["config"]["process_grid"] == "2x4" and out["scaling"] == "strong"
     assert "64x64x16 cells global (32x16x16 on rank 0)" in out["config"]["workload"]
