@@ -952,8 +952,7 @@ static int enqueue_iteration_k32(tsx_solver *s, bool first, bool half_ok) {
   const float *rhat = (const float *)s->vrhat;
   float *ph = (float *)s->vph, *sh = (float *)s->vsh;
   // with the scan passes the updates of p and s run cell by cell and leave the passes' bf16-pair words too
-  const bool words = s->pc_split && s->coef_h_scan && tsx_pcs_rhs16(s) && s->pc_sweeps + 1 >= 6 &&
-                     !(getenv("TSX_PC_WORDS") && atoi(getenv("TSX_PC_WORDS")) == 0);
+  const bool words = s->pc_split && s->coef_h_scan && s->pc_sweeps + 1 >= 6;
   const int nbc = grid_for(g.Nc);
   const bool half = half_ok && tsx_half_exit();
   double *hp = half ? s->partials : (double *)nullptr;
@@ -1380,12 +1379,11 @@ static int prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o)
   // Jacobi refinement and pc_coeff_fp16 = 0 work on fp64 directions and the exact blocks
   s->mixed = o->fp32_directions != 0 && !(o->pc == TSX_PC_COLUMN && o->pc_sweeps > 1) &&
              (o->pc == TSX_PC_NONE || o->pc_coeff_fp16 != 0);
-  // fp32 recurrence vectors too (fp32_directions = 2): with a preconditioner on the fp32 path; TSX_K32=0 falls back to 1
+  // fp32 recurrence vectors too (fp32_directions = 2): with a preconditioner on the fp32 path
   // ... and for tolerances an fp32 recurrence reaches between two replacements (rtol >= 1e-7: the reference's default is 1e-5);
   // tighter solves keep the fp64 recurrence -- every replacement costs BiCGStab some of its super-linear convergence (a
   // 130-level column at rtol 1e-10: 36 instead of 30 iterations)
-  s->k32 = s->mixed && o->fp32_directions >= 2 && o->pc != TSX_PC_NONE && !o->explicit_solver && o->rtol >= 1e-7 &&
-           !(getenv("TSX_K32") && atoi(getenv("TSX_K32")) == 0);
+  s->k32 = s->mixed && o->fp32_directions >= 2 && o->pc != TSX_PC_NONE && !o->explicit_solver && o->rtol >= 1e-7;
   // red-black ordering exists on the packed path; it needs an even number of columns per row, and an even
   // number of rows where the rank wraps onto itself in y (a periodic seam between equal colours) -- else zebra rows
   if (s->pc == TSX_PC_REDBLACK) {
@@ -1414,7 +1412,7 @@ static int prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o)
     // passes need 6 iterations where 10 need 10 -- and 10 passes with the one-lane-per-column kernels (zebra rows, odd grids)
     const bool scan = s->pc == TSX_PC_REDBLACK && s->mixed && tsx_pcs_eligible(s);
     const bool exact_scan = s->pc == TSX_PC_REDBLACK && !s->mixed;  // tsx_pcx.hip: the pass count measured in round 6 (profiles/r06)
-    // round 3: with the side -> top couplings in fp16 (3_10 scan kernels, C16) the residual after 5 iterations of 20 passes
+    // round 3: with the side -> top couplings in fp16 (3_10 scan kernels, tsx_k_pcs_pack_rec1h) the residual after 5 iterations of 20 passes
     // sits at 1.02-1.08e-5 on every measured domain -- 22 passes take it below the reference's rtol 1e-5: 5 iterations instead
     // of 6 (256 x 256 x 64: 18.7 -> 16.4 ms; 128 x 128: 6.05 -> 5.29 ms; all blocks distinct: 35.7 -> 31.5 ms; 24 / 26 passes:
     // still 5 iterations, 17.2 / 17.8 ms)
@@ -1548,9 +1546,9 @@ extern "C" int tsx_algorithmic_bytes(const tsx_solver *s, int kernel, double *by
     //         8_16 all passes: 12 (14) records -> 4 B (+192 / 224 per distinct set and pass)
     const bool h = g.ntop == 8;
     const double cell[2][2][4] = {{{200, 104, 224, 320}, {88, 72, 116, 212}}, {{544, 400, 624, 768}, {292, 276, 372, 516}}};
-    // 3_10 with the side -> top couplings in fp16 (C16): one record more per cell / per distinct block in the passes that read them
+    // 3_10 with the side -> top couplings in fp16: one record more per cell / per distinct block in the passes that read them
     // (8_16: four records more, 64 B)
-    const double c16 = s->coef_h_c16 ? (h ? 64.0 : 16.0) : 0.0;
+    const double c16 = s->coef_h_scan ? (h ? 64.0 : 16.0) : 0.0;
     const double ent[2][2] = {{112.0 + c16, 32}, {256.0 + c16, 128}};
     double c[4] = {cell[h][dd][0], cell[h][dd][1], cell[h][dd][2], cell[h][dd][3]};
     if (!dd) c[0] += c16, c[2] += c16, c[3] += c16;  // every pass with neighbours reads the extra record per cell
@@ -1571,7 +1569,7 @@ extern "C" int tsx_algorithmic_bytes(const tsx_solver *s, int kernel, double *by
     const double ngs = P > 3 ? P - 3 : 0;
     // bf16 right-hand side of the intermediate passes (tsx_k_pcs_rb RQ): a colour's first visit leaves 5 words (+20 B), the
     // later intermediate visits read 20 B instead of 40 B
-    const bool r16 = tsx_pcs_rhs16(s) && P >= 6;
+    const bool r16 = P >= 6;
     const double w16 = h ? 32.0 : 20.0;  // the bf16-pair words of a cell
     const double gs_b = r16 ? c[0] - w16 : c[0];
     if (kernel == 3) *bytes = gs_b * half + e_gs;
@@ -1635,7 +1633,7 @@ static int bench_kernel_t(tsx_solver *s, int kernel, int reps, float *avg_ms) {
     HIPCHK(hipEventRecord(s->ev0, s->stream));
     for (int q = 0; q < reps; ++q) {
       if (kernel == 2) rc = tsx_pc_apply(s, s->vp, s->vph, true, false);
-      else if (kernel == 3) rc = tsx_pcs_pass(s, 2 + (q & 1), 0, (float *)s->vph, nullptr, tsx_pcs_rhs16(s) ? 2 : 0);
+      else if (kernel == 3) rc = tsx_pcs_pass(s, 2 + (q & 1), 0, (float *)s->vph, nullptr, 2);
       else rc = tsx_pcs_flow(s, fl[3], fl[1], fl[2], nullptr);
       if (rc) return rc;
     }

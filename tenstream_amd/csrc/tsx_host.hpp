@@ -181,7 +181,6 @@ int tsx_allreduce_host(tsx_solver *s, double *v, int n);  // tsx_api.hip (tsx_pi
 int tsx_pcs_pack(tsx_solver *s);
 int tsx_pcs_apply(tsx_solver *s, float *z, const int *done);
 int tsx_pcs_pass(tsx_solver *s, int pass, int mode, float *zfin, const int *done, int rq, int part = 0);
-bool tsx_pcs_rhs16(const tsx_solver *s);
 // passes [p0, p1) of an application (all of them intermediate Gauss-Seidel passes on the bf16 right-hand side words) as ONE
 // launch of tsx_k_pcs_flow (tsx_pcs_flow.hip); tsx_pcs_flow_ok: can this solver's current scan configuration take it
 // solves in flight in this process (several solver instances on streams of their own: config 4's spectral loop)

@@ -21,12 +21,12 @@
 // be in flight at once, there are NSEG x as many waves, and small domains (config 2: 8192 columns per pass) fill the chip
 // with CW = 16 or 32.  Lanes still run along x: all accesses stay coalesced.
 //
-// Packed layout "S16" (8 records of 16 B per cell, colour-split order tsx_split_col), P[grp * Nc + cell]:
+// Packed layout "S16" (9 records of 16 B per cell, colour-split order tsx_split_col), P[grp * Nc + cell]:
 //   grp 0: E F G-1 H GT A_{k+1} A_k 0 (fp16)
-//   grp 1: c(y_q->0) c(y_q->1), q = 0..3 | c(x_q->0) c(x_q->1), q = 0..3  (fp8 e4m3 x 64)     (y_q = src dof 6+q, x_q = 2+q)
+//   grp 1: c(y_q->0) c(y_q->1), q = 0..3 (fp16)   grp 8: the same for x_q     (y_q = src dof 6+q, x_q = 2+q; tsx_k_pcs_pack_rec1h)
 //   grp 2: c(0 -> side d), d = 2..9 (fp16)        grp 3: c(1 -> side d) (fp16)
 //   grp 4, 5: c(y_q -> side 2+dd), byte 4 dd + q (fp8)       grp 6, 7: c(x_q -> side 2+dd) (fp8)
-// 1-D layers (src/pprts_shell.F90:417-427): grp 0 from a11 / a12, groups 1..7 zero -- the kernels need no 1-D branch.
+// 1-D layers (src/pprts_shell.F90:417-427): grp 0 from a11 / a12, groups 1..8 zero -- the kernels need no 1-D branch.
 // Iterates: the 8 side streams of a cell are stored as four records by the neighbour that consumes them,
 //   rec 0 = dofs (2, 4) -> read by the west neighbour,  1 = (3, 5) -> east,  2 = (6, 8) -> south,  3 = (7, 9) -> north,
 // bf16 pairs (4 B) in zb for the intermediate passes, float2 in z for the last two: a neighbour value costs one load per
@@ -115,44 +115,7 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_pcs_pack(TsxGeo g, const CT *
   }
 }
 
-// ---- the same groups 1..7 per *distinct* block (tsx_dedup.hip): PE[(grp - 1) * nent + id]; an entry whose representative
-// cell lies in a 1-D layer stands for all 1-D cells: zero records
-static __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_pcs_pack_ent(int ncol, long long nent, const float *__restrict__ Cd,
-                                                                const int *__restrict__ ent_cell, const uint8_t *__restrict__ l1d,
-                                                                uint4 *__restrict__ PE) {
-  constexpr int D = 10;
-  const long long n = nent * 7;
-  for (long long q = (long long)blockIdx.x * TSX_BLOCK + threadIdx.x; q < n; q += (long long)gridDim.x * TSX_BLOCK) {
-    const int grp = 1 + (int)(q / nent);
-    const long long id = q - (long long)(grp - 1) * nent;
-    const int k = ent_cell[id] / ncol;
-    auto cf = [&](int dst, int src) { return Cd[(size_t)(dst * D + src) * nent + id]; };
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (!l1d[k]) {
-      if (grp == 1) {
-        v.x = tsx_to_fp8x4(cf(0, 6), cf(1, 6), cf(0, 7), cf(1, 7));
-        v.y = tsx_to_fp8x4(cf(0, 8), cf(1, 8), cf(0, 9), cf(1, 9));
-        v.z = tsx_to_fp8x4(cf(0, 2), cf(1, 2), cf(0, 3), cf(1, 3));
-        v.w = tsx_to_fp8x4(cf(0, 4), cf(1, 4), cf(0, 5), cf(1, 5));
-      } else if (grp == 2 || grp == 3) {
-        const int s = grp - 2;
-        v.x = tsx_to_h2(cf(2, s), cf(3, s));
-        v.y = tsx_to_h2(cf(4, s), cf(5, s));
-        v.z = tsx_to_h2(cf(6, s), cf(7, s));
-        v.w = tsx_to_h2(cf(8, s), cf(9, s));
-      } else {
-        const int s0 = grp < 6 ? 6 : 2, d0 = 2 + 4 * ((grp - 4) & 1);
-        v.x = tsx_to_fp8x4(cf(d0 + 0, s0), cf(d0 + 0, s0 + 1), cf(d0 + 0, s0 + 2), cf(d0 + 0, s0 + 3));
-        v.y = tsx_to_fp8x4(cf(d0 + 1, s0), cf(d0 + 1, s0 + 1), cf(d0 + 1, s0 + 2), cf(d0 + 1, s0 + 3));
-        v.z = tsx_to_fp8x4(cf(d0 + 2, s0), cf(d0 + 2, s0 + 1), cf(d0 + 2, s0 + 2), cf(d0 + 2, s0 + 3));
-        v.w = tsx_to_fp8x4(cf(d0 + 3, s0), cf(d0 + 3, s0 + 1), cf(d0 + 3, s0 + 2), cf(d0 + 3, s0 + 3));
-      }
-    }
-    PE[q] = v;
-  }
-}
-
-// ---- side -> top couplings in fp16 (C16).  tests/studies/quant_study.py: of everything the preconditioner rounds, only the
+// ---- side -> top couplings in fp16.  tests/studies/quant_study.py: of everything the preconditioner rounds, only the
 // precision of the couplings from the neighbouring columns' side streams INTO the column's top streams (record 1) costs
 // iterations -- they feed the exact column solve, which spreads their error through the whole column: 3 iterations with
 // them exact or fp16 against 4 with fp8 e4m3 on 64 x 64 x 32 (the device: 4), 6 -> 5 on 256 x 256 x 64; the 64 side -> side
@@ -256,8 +219,8 @@ __device__ __forceinline__ unsigned tsx_bf16x2(float lo, float hi) {
 // (`buffer_load_dword v, v_off, s[rsrc:rsrc+3], 0 offen`).  The base lives in scalar registers and the byte offset is formed in
 // 32 bits, so an access costs no vector instruction of address arithmetic -- with plain pointers an intermediate pass of
 // tsx_k_pcs_rb spent one v_lshl_add_u64 per load and store (140 of its 1770 vector instructions), and the pass is bound by its
-// vector instructions (scripts/fold_probe.sh).  Needs i * sizeof(T) < 2^32, which pcs_config checks (Nc < 2^26).  The
-// descriptor: stride 0, no range limit, gfx9 dword 3 (data format 32).
+// vector instructions ("What bounds a pass").  Needs i * sizeof(T) < 2^32, which pcs_config checks
+// (Nc < 2^26).  The descriptor: stride 0, no range limit, gfx9 dword 3 (data format 32).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tsx_rsrc(const void *base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, -1, 0x00020000);
 }
@@ -409,47 +372,10 @@ __device__ __forceinline__ bool tsx_pcs_on_frame(const TsxGeo &g, int jrow, int 
 // right-hand side as five bf16-pair words per cell, rb[w * Nc + cell] = (ru, rd), (rs0, rs1) .. (rs6, rs7): 20 B instead of
 // 40 B.  RQ 1: the colour's first visit reads fp32 and leaves those words; RQ 2: reads them; RQ 0: fp32 only.  (Measured:
 // rounding the intermediate passes' right-hand side to bf16 changes no iteration count, 8 / 13 at rtol 1e-5 / 1e-8.)
-// C16: the side -> top couplings (record 1) are two fp16 records (tsx_k_pcs_pack_rec1h / tsx_k_pcs_pack_ent16).
+// The side -> top couplings (record 1) are two fp16 records (tsx_k_pcs_pack_rec1h / tsx_k_pcs_pack_ent16).
 // PEER (MODE 0 / 1, peer transport): the columns on a rank face store the records their neighbour rank consumes straight into
 // that rank's mailbox slot (what tsx_k_pcs_halo_pack + tsx_k_peer_send would do after the pass), the workgroup that finishes
 // last publishes the sequence numbers -- an exchange without a kernel of its own (tsx_peer_dev.hpp; snd: this pass's messages).
-// Analysis builds only (scripts/fold_probe.sh; never the shipped library): -DTSX_PCS_FOLD=2^n wraps the per-cell streams of an
-// intermediate pass (right-hand side words, neighbour records, stored records) onto the first 2^n cells of their planes, so that they
-// are served by L2 and what remains of the pass's time is its table gathers and arithmetic; -DTSX_PCS_FOLD_IDX wraps the record
-// index too (the gathers then hit L1).  The results are meaningless.
-#ifndef TSX_PCS_PROBE
-#define TSX_PCS_PROBE 0  // analysis builds (scripts/pass_parts.sh): bit 0 no side-stream right-hand side loads in phase 3, 1 no stores of
-#endif                   // the intermediate passes, 2 no neighbour loads, 3 every lane the block entry 0, 4 every lane record 0 of PT, 5 one store per thread
-#ifndef TSX_PCS_COOP
-#define TSX_PCS_COOP 1  // 0: entry-major per-block records gathered lane by lane also in phase 3 (A/B builds)
-#endif
-#ifndef TSX_PCS_STAGED
-#define TSX_PCS_STAGED 0  // 1: the staged order of phase 1's loads for every layout (A/B builds)
-#endif
-#ifdef TSX_PCS_FOLD
-#define TSX_FOLDC(x) ((size_t)(x) & (size_t)(TSX_PCS_FOLD - 1))
-#else
-#define TSX_FOLDC(x) (x)
-#endif
-#ifdef TSX_PCS_FOLD_IDX
-#define TSX_FOLDI(x) TSX_FOLDC(x)
-#else
-#define TSX_FOLDI(x) (x)
-#endif
-// -DTSX_FLOW_TRACE (analysis builds, scripts/flow_trace.sh): thread 0 of a flow workgroup leaves wall-clock stamps of the stages of
-// every work item in tsx_flow_tl
-#ifdef TSX_FLOW_TRACE
-#define TSX_FLOW_TL_N 32768
-__device__ unsigned long long tsx_flow_tl[TSX_FLOW_TL_N][12];
-#define TSX_TL(k)                                                  \
-  do {                                                             \
-    if (FLOW && tl && threadIdx.x == 0) tl[k] = wall_clock64();    \
-  } while (0)
-#else
-#define TSX_TL(k) \
-  do {            \
-  } while (0)
-#endif
 // FLOW (tsx_k_pcs_flow below: the intermediate passes of one application inside ONE launch, a workgroup per (pass, tile) work
 // item): the iterate records and right-hand side words another workgroup of the same launch wrote or will read travel as sc1
 // (write-through) stores and sc1 loads -- a CU's L1 is never refreshed by another CU's stores and the XCDs' L2s are not coherent
@@ -476,25 +402,23 @@ struct TsxGran {
   unsigned long long ticks;
   int *err;
 };
-template <int LSEG, int NSEG, int CW, bool GS, int MODE, bool IDX, int RQ, bool C16, bool PEER, bool FLOW, bool HOIST = false,
+template <int LSEG, int NSEG, int CW, bool GS, int MODE, bool IDX, int RQ, bool PEER, bool FLOW, bool HOIST = false,
           typename WaitF = TsxNoWait, bool GRAN = false>
 __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__restrict__ P, const float *__restrict__ r,
                                                 float *__restrict__ z, unsigned *__restrict__ zb, float *__restrict__ zfin, int rbc,
                                                 int nonbr, const int *__restrict__ cidx, long long nent,
                                                 const uint4 *__restrict__ PE, const TsxPcHalo &hal, unsigned *__restrict__ rb,
                                                 int part, const int *__restrict__ pidx, const uint4 *__restrict__ PT,
-                                                const TsxPeerXArgs &snd, int pe_si, int tile,
-                                                unsigned long long *tl = nullptr, WaitF wait_nbrs = WaitF(),
+                                                const TsxPeerXArgs &snd, int pe_si, int tile, WaitF wait_nbrs = WaitF(),
                                                 const TsxGran *gr = nullptr) {
-  (void)tl;
   static_assert(!GRAN || HOIST, "granules: the flow kernel's fat body");
-  static_assert(!HOIST || (FLOW && GS && MODE == 0 && RQ == 2 && C16), "HOIST: an intermediate pass of the flow kernel");
+  static_assert(!HOIST || (FLOW && GS && MODE == 0 && RQ == 2), "HOIST: an intermediate pass of the flow kernel");
   static_assert(!PEER || MODE != 2, "the last pass sends nothing");
   static_assert(!FLOW || MODE == 0, "the flow kernel runs intermediate passes");
   // (round 6: rank faces inside the flow kernel with the lean body too -- shards whose passes are not resident at once; it sends
   // after the scan like the 32-column pass kernel, the fat body from the level loop)
   constexpr int XA = FLOW ? 16 : 0;  // aux of the accesses another workgroup of the launch is on the other end of: sc1
-  // per-block records: PE[slot * pe_ss + id * pe_si]; pe_si = 1: slot-major planes of nent entries, pe_si = 8 (C16 only):
+  // per-block records: PE[slot * pe_ss + id * pe_si]; pe_si = 1: slot-major planes of nent entries, pe_si = 8:
   // entry-major, an entry's eight records in one 128-byte line (tsx_k_pcs_pack_ent16)
   const size_t pe_ss = pe_si == 1 ? (size_t)nent : (size_t)1;
   // pidx != null (intermediate passes with shared blocks): the cell's record 0 (with its block index) is entry pidx[cell] of
@@ -502,14 +426,13 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
   static_assert(RQ == 0 || MODE == 0, "bf16 right-hand side only in the intermediate passes");
   constexpr int D = 10, NTOP = 2;
   constexpr bool FINAL = MODE == 2;
-  constexpr float CSC1 = C16 ? 1.0f : 1.0f / TSX_FP8_SCALE;  // the fp8 couplings are stored times TSX_FP8_SCALE
   __shared__ float2 sB[NSEG][CW], sV[NSEG][CW];
   // COOP (entry-major per-block records, pe_si = 8: every lane another 128-byte entry -- the near-identical grouping of a field
   // without identical blocks): the six records of phase 3 are fetched by groups of eight lanes, lane j of a group the record 2 + j
   // of the entry of the group's t-th lane, t = 0..7 -- an instruction touches 8 lines instead of 64 (the texture addresser is
   // 80 % busy there, one tag look-up per lane and gather) -- and handed to their lanes through LDS (rows of 7 records: no bank
   // conflicts on the way out).  One wave's rows are private to it: LDS executes a wave's instructions in order, no barrier.
-  constexpr bool COOP = TSX_PCS_COOP && IDX && C16 && GS && !PEER && !HOIST && (CW == 32 || CW == 16) && (CW * NSEG) % 64 == 0;
+  constexpr bool COOP = IDX && GS && !PEER && !HOIST && (CW == 32 || CW == 16) && (CW * NSEG) % 64 == 0;
   __shared__ uint4 sE[COOP ? CW * NSEG / 64 : 1][COOP ? 64 * 7 : 1];
   // Lane offsets are 32-bit (tsx_ldu / tsx_stu), plane bases 64-bit and wave-uniform.
   const int h = g.xm >> 1;
@@ -589,7 +512,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
     for (int m = 0; m < 4; ++m) {
       const unsigned ci = (unsigned)((int)c + off[m]);
       if (MODE == 2) o[m] = tsx_ldo(reinterpret_cast<const uint2 *>(zr), (size_t)m * Nc, ci);
-      else o[m] = make_uint2((TSX_PCS_PROBE & 4) ? 0x3f803f80u : tsx_ldo<unsigned, XA>(zb, (size_t)m * Nc, (unsigned)TSX_FOLDC(ci)), 0u);
+      else o[m] = make_uint2(tsx_ldo<unsigned, XA>(zb, (size_t)m * Nc, ci), 0u);
     }
   };
   auto nbr_halo = [&](int k, unsigned (&hv)[4]) {  // unconditional loads from valid addresses
@@ -628,24 +551,19 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
   };
 
   // ---- phase 1: all loads of the upward scan (independent of each other), then the local scan with zero inflow
-  uint4 r0[LSEG], r1[LSEG], r1x[C16 ? LSEG : 1];
+  uint4 r0[LSEG], r1[LSEG], r1x[LSEG];
   float ru[LSEG], rd[LSEG];
   uint2 nb[LSEG][4];
   unsigned eid[LSEG];  // (times pe_si: the lane offset into a slot of the per-block records)
-  // group g = 1..7 of the layout: per cell P[g * Nc + cell]; per block PE[(g - 1) * nent + id], or with C16 PE[g * nent + id]
-  // (slots 0 and 1 hold record 1's two fp16 halves)
+  // group g = 2..7 of the layout: per cell P[g * Nc + cell]; per block PE[g * nent + id] (slots 0 and 1 hold record 1's two
+  // fp16 halves).  Planes in fours per descriptor, the plane within the four as scalar offset
   auto rec = [&](int grp, unsigned c, unsigned ei) {
-    const int slot = C16 ? grp : grp - 1;  // planes in fours per descriptor, the plane within the four as scalar offset
-    return IDX ? tsx_ldo(PE + (size_t)(slot & ~3) * pe_ss, (size_t)(slot & 3) * pe_ss, ei) : tsx_ldo(P + (size_t)(grp & ~3) * Nc, (size_t)(grp & 3) * Nc, c);
+    return IDX ? tsx_ldo(PE + (size_t)(grp & ~3) * pe_ss, (size_t)(grp & 3) * pe_ss, ei) : tsx_ldo(P + (size_t)(grp & ~3) * Nc, (size_t)(grp & 3) * Nc, c);
   };
-  // four side -> top couplings as floats: fp8 word w, or the fp16 pair of words (a, b)
-  auto dec4 = [&](unsigned w, unsigned a, unsigned b, float (&o)[4]) {
-    if (C16) {
-      const tsx_h4 h = __builtin_bit_cast(tsx_h4, make_uint2(a, b));
-      o[0] = (float)h[0]; o[1] = (float)h[1]; o[2] = (float)h[2]; o[3] = (float)h[3];
-    } else {
-      tsx_fp8x4(w, o);
-    }
+  // four side -> top couplings as floats from the fp16 pair of words (a, b)
+  auto dec4 = [&](unsigned a, unsigned b, float (&o)[4]) {
+    const tsx_h4 h = __builtin_bit_cast(tsx_h4, make_uint2(a, b));
+    o[0] = (float)h[0]; o[1] = (float)h[1]; o[2] = (float)h[2]; o[3] = (float)h[3];
   };
   // The loads are written stage by stage over the levels (indices -> independent words -> records behind the indices), with
   // the wave-uniform decisions outside the loops: a branch per level fences the levels' loads off from each other, and a
@@ -727,12 +645,12 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
       for (int l = 0; l < LSEG; ++l) nbr_select(nb[l], none, false);
     }
   } else
-  if (TSX_PCS_STAGED || pe_si == 1) {
+  if (pe_si == 1) {
   unsigned pi[LSEG];
   if (IDX && MODE == 0) {
     if (pidx) {
 #pragma unroll
-      for (int l = 0; l < LSEG; ++l) pi[l] = (TSX_PCS_PROBE & 16) ? 0u : (unsigned)tsx_ldu(pidx, (unsigned)TSX_FOLDI(cell(l)));
+      for (int l = 0; l < LSEG; ++l) pi[l] = (unsigned)tsx_ldu(pidx, cell(l));
     }
   } else if (IDX) {
 #pragma unroll
@@ -742,7 +660,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
   for (int l = 0; l < LSEG; ++l) {
     const unsigned c = cell(l);
     if (RQ == 2) {
-      const unsigned w = tsx_ldu<unsigned, XA>(rb, (unsigned)TSX_FOLDC(c));
+      const unsigned w = tsx_ldu<unsigned, XA>(rb, c);
       ru[l] = __uint_as_float(w << 16);
       rd[l] = __uint_as_float(w & 0xffff0000u);
     } else {
@@ -760,7 +678,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
       for (int l = 0; l < LSEG; ++l) r0[l] = tsx_ldo(P + (size_t)4 * Nc, (size_t)3 * Nc, cell(l));
     }
 #pragma unroll
-    for (int l = 0; l < LSEG; ++l) eid[l] = (TSX_PCS_PROBE & 8) ? 0u : r0[l].w * (unsigned)pe_si;
+    for (int l = 0; l < LSEG; ++l) eid[l] = r0[l].w * (unsigned)pe_si;
   } else {
 #pragma unroll
     for (int l = 0; l < LSEG; ++l) {
@@ -772,12 +690,8 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
 #pragma unroll
     for (int l = 0; l < LSEG; ++l) {
       const unsigned c = cell(l);
-      if (C16) {
-        r1[l] = IDX ? tsx_ldu(PE, eid[l]) : tsx_ldo(P, Nc, c);
-        r1x[l] = IDX ? tsx_ldo(PE, pe_ss, eid[l]) : tsx_ldu(P + (size_t)8 * Nc, c);
-      } else {
-        r1[l] = rec(1, c, eid[l]);
-      }
+      r1[l] = IDX ? tsx_ldu(PE, eid[l]) : tsx_ldo(P, Nc, c);
+      r1x[l] = IDX ? tsx_ldo(PE, pe_ss, eid[l]) : tsx_ldu(P + (size_t)8 * Nc, c);
     }
     if (anyface) {
 #pragma unroll
@@ -798,14 +712,14 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
     for (int l = 0; l < LSEG; ++l) {
       const unsigned c = cell(l);
       if (IDX && MODE == 0) {
-        r0[l] = pidx ? tsx_ldu(PT, (unsigned)tsx_ldu(pidx, (unsigned)TSX_FOLDI(c))) : tsx_ldo(P + (size_t)4 * Nc, (size_t)3 * Nc, c);
+        r0[l] = pidx ? tsx_ldu(PT, (unsigned)tsx_ldu(pidx, c)) : tsx_ldo(P + (size_t)4 * Nc, (size_t)3 * Nc, c);
         eid[l] = r0[l].w * (unsigned)pe_si;
       } else {
         eid[l] = IDX ? (unsigned)tsx_ldu(cidx, c) * (unsigned)pe_si : 0u;
         r0[l] = tsx_ldu(P, c);
       }
       if (RQ == 2) {
-        const unsigned w = tsx_ldu<unsigned, XA>(rb, (unsigned)TSX_FOLDC(c));
+        const unsigned w = tsx_ldu<unsigned, XA>(rb, c);
         ru[l] = __uint_as_float(w << 16);
         rd[l] = __uint_as_float(w & 0xffff0000u);
       } else {
@@ -813,12 +727,8 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
         rd[l] = tsx_ldo(r, Nc, c);
       }
       if (GS) {
-        if (C16) {
-          r1[l] = IDX ? tsx_ldu(PE, eid[l]) : tsx_ldo(P, Nc, c);
-          r1x[l] = IDX ? tsx_ldo(PE, pe_ss, eid[l]) : tsx_ldu(P + (size_t)8 * Nc, c);
-        } else {
-          r1[l] = rec(1, c, eid[l]);
-        }
+        r1[l] = IDX ? tsx_ldu(PE, eid[l]) : tsx_ldo(P, Nc, c);
+        r1x[l] = IDX ? tsx_ldo(PE, pe_ss, eid[l]) : tsx_ldu(P + (size_t)8 * Nc, c);
         nbr_load(c, nb[l]);
         unsigned hv[4] = {0u, 0u, 0u, 0u};
         if (anyface) nbr_halo(level(l), hv);
@@ -841,17 +751,17 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
       if (GS) {
         float zx[4], zy[4], cy0[4], cy1[4], cx0[4], cx1[4];
         nbr_vals(nb[l], zx, zy);
-        const uint4 ry = r1[l], rx = C16 ? r1x[l] : r1[l];
-        dec4(ry.x, ry.x, ry.y, cy0);
-        dec4(ry.y, ry.z, ry.w, cy1);
-        dec4(rx.z, rx.x, rx.y, cx0);
-        dec4(rx.w, rx.z, rx.w, cx1);
+        const uint4 ry = r1[l], rx = r1x[l];
+        dec4(ry.x, ry.y, cy0);
+        dec4(ry.z, ry.w, cy1);
+        dec4(rx.x, rx.y, cx0);
+        dec4(rx.z, rx.w, cx1);
         float gu8 = cy0[0] * zy[0] + cy0[2] * zy[1] + cy1[0] * zy[2] + cy1[2] * zy[3];
         float gd8 = cy0[1] * zy[0] + cy0[3] * zy[1] + cy1[1] * zy[2] + cy1[3] * zy[3];
         gu8 += cx0[0] * zx[0] + cx0[2] * zx[1] + cx1[0] * zx[2] + cx1[2] * zx[3];
         gd8 += cx0[1] * zx[0] + cx0[3] * zx[1] + cx1[1] * zx[2] + cx1[3] * zx[3];
-        gu = gu8 * CSC1;
-        gd = gd8 * CSC1;
+        gu = gu8;
+        gd = gd8;
       }
       const bool act = l < nl;
       const float E = act ? (float)m[0] : 1.0f;
@@ -865,9 +775,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
     }
     sB[sg][cl] = make_float2(Bl, Pc);
   }
-  TSX_TL(3);
   __syncthreads();
-  TSX_TL(4);
   float Bin = rsurf;  // B at the level below this segment
   for (int s2 = NSEG - 1; s2 > sg; --s2) {
     const float2 v = sB[s2][cl];
@@ -894,7 +802,6 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
     sV[sg][cl] = make_float2(Vl, Qc);
   }
   __syncthreads();
-  TSX_TL(5);
   float Vin = V0;  // V at the top level of this segment
   for (int s2 = 0; s2 < sg; ++s2) {
     const float2 v = sV[s2][cl];
@@ -917,7 +824,6 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
   // top of the kernel straight into LDS (`buffer_load_dword ... lds`): 30.1 -> 32.7 us -- the pass is bound by the texture
   // addresser's cycles (TA busy 65-74 %, scripts/pass_pmc.sh), not by the latency of this chain, and each DMA is one more
   // vector-memory instruction)
-  float probe_acc = 0.0f;
   float V = Vin;
 #pragma unroll
   for (int l = 0; l < LSEG; ++l) {
@@ -972,7 +878,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
     if (RQ == 2) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const unsigned w = HOIST ? hrs[HOIST ? l : 0][q] : (TSX_PCS_PROBE & 1) ? 0x3f803f80u : tsx_ldo<unsigned, XA>(rb, (size_t)(1 + q) * Nc, (unsigned)TSX_FOLDC(c));
+        const unsigned w = HOIST ? hrs[HOIST ? l : 0][q] : tsx_ldo<unsigned, XA>(rb, (size_t)(1 + q) * Nc, c);
         rs[2 * q] = __uint_as_float(w << 16);
         rs[2 * q + 1] = __uint_as_float(w & 0xffff0000u);
       }
@@ -1027,10 +933,6 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
       zo[dd] = rs[dd] + acc;
     }
     // records: (2,4) (3,5) (6,8) (7,9)  = zo[0,2] zo[1,3] zo[4,6] zo[5,7]
-    if (MODE == 0 && (TSX_PCS_PROBE & 32)) {  // one store per thread instead of four per level: what the stores cost
-      probe_acc += zo[0] + zo[1] + zo[2] + zo[3] + zo[4] + zo[5] + zo[6] + zo[7];
-      if (l == LSEG - 1 && st) tsx_sto(zb, (size_t)0, (unsigned)TSX_FOLDC(c), __float_as_uint(probe_acc));
-    } else
     if (GRAN) {
       if (st) {
         const unsigned w4[4] = {tsx_bf16x2(zo[0], zo[2]), tsx_bf16x2(zo[1], zo[3]), tsx_bf16x2(zo[4], zo[6]), tsx_bf16x2(zo[5], zo[7])};
@@ -1042,11 +944,11 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
         }
       }
     } else
-    if (MODE == 0 && st && !(TSX_PCS_PROBE & 2)) {
-      tsx_sto<unsigned, XA>(zb, (size_t)0 * Nc, (unsigned)TSX_FOLDC(c), tsx_bf16x2(zo[0], zo[2]));
-      tsx_sto<unsigned, XA>(zb, (size_t)1 * Nc, (unsigned)TSX_FOLDC(c), tsx_bf16x2(zo[1], zo[3]));
-      tsx_sto<unsigned, XA>(zb, (size_t)2 * Nc, (unsigned)TSX_FOLDC(c), tsx_bf16x2(zo[4], zo[6]));
-      tsx_sto<unsigned, XA>(zb, (size_t)3 * Nc, (unsigned)TSX_FOLDC(c), tsx_bf16x2(zo[5], zo[7]));
+    if (MODE == 0 && st) {
+      tsx_sto<unsigned, XA>(zb, (size_t)0 * Nc, c, tsx_bf16x2(zo[0], zo[2]));
+      tsx_sto<unsigned, XA>(zb, (size_t)1 * Nc, c, tsx_bf16x2(zo[1], zo[3]));
+      tsx_sto<unsigned, XA>(zb, (size_t)2 * Nc, c, tsx_bf16x2(zo[4], zo[6]));
+      tsx_sto<unsigned, XA>(zb, (size_t)3 * Nc, c, tsx_bf16x2(zo[5], zo[7]));
     }
     if constexpr (PEER && (FLOW ? HOIST : CW < 32)) {
       // small passes (16-column workgroups: at most one workgroup per CU's worth of columns, latency-bound, registers to spare):
@@ -1126,7 +1028,7 @@ __device__ __forceinline__ void tsx_pcs_rb_body(const TsxGeo &g, const uint4 *__
 }
 
 // one pass per launch: a workgroup per CW columns of the colour
-template <int LSEG, int NSEG, int CW, bool GS, int MODE, bool IDX = false, int RQ = 0, bool C16 = false, bool PEER = false>
+template <int LSEG, int NSEG, int CW, bool GS, int MODE, bool IDX = false, int RQ = 0, bool PEER = false>
 __global__ __launch_bounds__(CW *NSEG, PEER && MODE == 0 && CW >= 32 ? 4 : 1) void tsx_k_pcs_rb(TsxGeo g, const uint4 *__restrict__ P, const float *__restrict__ r,
                                                          float *__restrict__ z, unsigned *__restrict__ zb,
                                                          float *__restrict__ zfin, const int *__restrict__ done, int rbc,
@@ -1135,8 +1037,8 @@ __global__ __launch_bounds__(CW *NSEG, PEER && MODE == 0 && CW >= 32 ? 4 : 1) vo
                                                          unsigned *__restrict__ rb, int part, const int *__restrict__ pidx,
                                                          const uint4 *__restrict__ PT, TsxPeerXArgs snd, int pe_si) {
   if (done && *done) return;
-  tsx_pcs_rb_body<LSEG, NSEG, CW, GS, MODE, IDX, RQ, C16, PEER, false>(g, P, r, z, zb, zfin, rbc, nonbr, cidx, nent, PE, hal, rb, part,
-                                                                       pidx, PT, snd, pe_si, (int)blockIdx.x);
+  tsx_pcs_rb_body<LSEG, NSEG, CW, GS, MODE, IDX, RQ, PEER, false>(g, P, r, z, zb, zfin, rbc, nonbr, cidx, nent, PE, hal, rb, part, pidx,
+                                                                  PT, snd, pe_si, (int)blockIdx.x);
 }
 
 // ---- the intermediate passes of one application as ONE launch ("flow" kernel, round 5).
@@ -1184,7 +1086,7 @@ struct TsxFlowArgs {
   const TsxFlowPeer *prp;           // device-resident: what does not change from launch to launch (the arguments live in scalar registers)
   unsigned long long R0[4], S0[4];  // messages received / sent through the faces before this launch
 };
-template <int LSEG, int NSEG, int CW, bool IDX, bool C16, bool FAT, bool GRANV = false, bool FPEER = false>
+template <int LSEG, int NSEG, int CW, bool IDX, bool FAT, bool GRANV = false, bool FPEER = false>
 __global__ __launch_bounds__(CW *NSEG, FAT ? 2 : 4) void tsx_k_pcs_flow(TsxGeo g, const uint4 *__restrict__ P,
                                                                         const float *__restrict__ r, unsigned *__restrict__ zb,
                                                                         const int *__restrict__ done, const int *__restrict__ cidx,
@@ -1220,17 +1122,6 @@ __global__ __launch_bounds__(CW *NSEG, FAT ? 2 : 4) void tsx_k_pcs_flow(TsxGeo g
   while (tk < nitems) {
     const unsigned pp = tk / ntiles, t = tk - pp * ntiles;
     const int rbc = (f.p0 + (int)pp) & 1;
-    [[maybe_unused]] constexpr bool FLOW = true;
-#ifdef TSX_FLOW_TRACE
-    unsigned long long *tl = tsx_flow_tl[tk % TSX_FLOW_TL_N];
-    if (threadIdx.x == 0) {
-      tl[0] = wall_clock64();
-      tl[10] = ((unsigned long long)pp << 32) | t;
-      tl[11] = (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) | ((unsigned long long)blockIdx.x << 8);  // XCC_ID
-    }
-#else
-    unsigned long long *tl = nullptr;
-#endif
     unsigned nxt = 0;
     if (threadIdx.x == 0) nxt = atomicAdd(&f.st->ticket, 1u);  // the next item's ticket travels under this item's work
     // wait for the four tiles of the other colour whose records this tile reads (and which read this tile's): same position, the
@@ -1325,16 +1216,10 @@ __global__ __launch_bounds__(CW *NSEG, FAT ? 2 : 4) void tsx_k_pcs_flow(TsxGeo g
           }
         }
       }
-      TSX_TL(1);
       __syncthreads();
-      TSX_TL(2);
     };
     if constexpr (FAT && GRANV) {
       // the records are their own flags (TsxGran): nothing to wait for in front of them, nothing to publish behind them
-      auto stamps = [&]() {
-        TSX_TL(1);
-        TSX_TL(2);
-      };
       TsxGran gr;
       gr.zb8 = f.zb8;
       gr.need = epoch + pp;
@@ -1343,32 +1228,26 @@ __global__ __launch_bounds__(CW *NSEG, FAT ? 2 : 4) void tsx_k_pcs_flow(TsxGeo g
       gr.last = (int)pp == f.p1 - f.p0 - 1;
       gr.ticks = f.ticks;
       gr.err = f.err;
-      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, C16, false, true, true, decltype(stamps), true>(
-          g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0, pidx, PT, snd, pe_si, (int)t, tl, stamps, &gr);
-      TSX_TL(6);
-      TSX_TL(7);
+      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, false, true, true, TsxNoWait, true>(
+          g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0, pidx, PT, snd, pe_si, (int)t, TsxNoWait(), &gr);
       if (threadIdx.x == 0) s_tk = nxt;
       __syncthreads();
-      TSX_TL(8);
       tk = s_tk;
       continue;
     } else if constexpr (FAT) {
-      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, C16, FPEER, true, true, decltype(wait_nbrs)>(
-          g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0, pidx, PT, snd, pe_si, (int)t, tl, wait_nbrs);
+      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, FPEER, true, true, decltype(wait_nbrs)>(
+          g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0, pidx, PT, snd, pe_si, (int)t, wait_nbrs);
     } else {
       wait_nbrs();
-      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, C16, FPEER, true>(g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0,
-                                                                         pidx, PT, snd, pe_si, (int)t, tl);
+      tsx_pcs_rb_body<LSEG, NSEG, CW, true, 0, IDX, 2, FPEER, true>(g, P, r, nullptr, zb, nullptr, rbc, 0, cidx, nent, PE, hal, rb, 0,
+                                                                    pidx, PT, snd, pe_si, (int)t);
     }
-    TSX_TL(6);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its records have left the XCD's L2
     if constexpr (FPEER) {
       if (pr.heavy) __threadfence_system();
     }
-    TSX_TL(7);
     if (threadIdx.x == 0) s_tk = nxt;
     __syncthreads();
-    TSX_TL(8);
     if (threadIdx.x == 0)
       __hip_atomic_store(f.prog + (size_t)rbc * ntiles + t, epoch + pp + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if constexpr (FPEER) {
@@ -1425,18 +1304,11 @@ __global__ __launch_bounds__(CW *NSEG, FAT ? 2 : 4) void tsx_k_pcs_flow(TsxGeo g
 // keeping a cumulative product per level).  Packed layout "S16H", 16-byte records:
 //   per cell, P[grp * Nc + cell] (fp16 4 x 4 row-major, two records each): 0,1 E | 2,3 F | 4,5 G - I | 6,7 H | 8,9 GT |
 //     10,11 A_{k+1} | 12,13 A_k
-//   per block, PB[grp * stride + (cell | entry)]: 0,1 c(y_q -> t), byte 4 t + q (fp8) | 2,3 c(x_q -> t) |
-//     4..11 c(src 0..7 -> side dst 8 + dd) (fp16) | 12,13 c(y_q -> 8 + dd), byte 4 dd + q | 14,15 c(x_q -> 8 + dd)
+//   per block, PB[grp * stride + (cell | entry)]: 0..3 c(y_q -> t), half 4 (t & 1) + q of record t >> 1 (fp16, see
+//     tsx_k_pcs_pack_rec1h) | 4..7 c(x_q -> t), the same in record 4 + (t >> 1) | 8..15 c(src 0..7 -> side dst 8 + dd) (fp16) |
+//     16,17 c(y_q -> 8 + dd), byte 4 dd + q (fp8) | 18,19 c(x_q -> 8 + dd)
 //   (y_q = src 12 + q, x_q = src 8 + q; t = top dst 0..7).  1-D layers: matrices from a11 / a12, block records zero.
-#ifndef TSX_PCS_C16
-#define TSX_PCS_C16 1  // side -> top couplings in fp16 (see tsx_k_pcs_pack_rec1h); 0: fp8 like the side -> side couplings
-#endif
-#ifndef TSX_PCSH_DEFER_ST
-#define TSX_PCSH_DEFER_ST 0  // 1 (A/B builds): the 8_16 intermediate passes store their four records per level behind phase 4's level loop -- the scheduler then hoists the levels' loads until 105 registers spill (256 VGPRs); off
-#endif
-// With TSX_PCS_C16 the four fp8 records 0..3 of the per-block part become eight fp16 records (two top dsts per record:
-// halfs 4 (t & 1) + q of record t >> 1 for the y sources, of record 4 + (t >> 1) for the x sources) and the others move up by four
-constexpr int TSX_S16H_CELL = 14, TSX_S16H_BLOCK = TSX_PCS_C16 ? 20 : 16, TSX_S16H_BO = TSX_PCS_C16 ? 4 : 0;
+constexpr int TSX_S16H_CELL = 14, TSX_S16H_BLOCK = 20;
 
 __device__ __forceinline__ uint4 tsx_pack_rows2(const double (&M)[4][4], int r0, double sub_diag) {
   auto v = [&](int a, int b) { return (float)(M[a][b] - (a == b ? sub_diag : 0.0)); };
@@ -1528,26 +1400,20 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_pcsh_pack_block(TsxGeo g, lon
     auto cf = [&](int dst, int src) { return (float)C[(size_t)(dst * D + src) * n + e]; };
     uint4 v = make_uint4(0, 0, 0, 0);
     if (!l1d[k]) {
-      if (TSX_PCS_C16 && grp < 8) {  // couplings into the top streams in fp16: record (t >> 1) [+ 4 for the x sources]
+      if (grp < 8) {  // couplings into the top streams in fp16: record (t >> 1) [+ 4 for the x sources]
         const int s0 = grp < 4 ? 12 : 8, t0 = 2 * (grp & 3);
         v.x = tsx_to_h2(cf(t0, s0), cf(t0, s0 + 1));
         v.y = tsx_to_h2(cf(t0, s0 + 2), cf(t0, s0 + 3));
         v.z = tsx_to_h2(cf(t0 + 1, s0), cf(t0 + 1, s0 + 1));
         v.w = tsx_to_h2(cf(t0 + 1, s0 + 2), cf(t0 + 1, s0 + 3));
-      } else if (!TSX_PCS_C16 && grp < 4) {  // couplings into the top streams: word t = the four side sources of top dst t
-        const int s0 = grp < 2 ? 12 : 8, t0 = 4 * (grp & 1);
-        v.x = tsx_to_fp8x4(cf(t0 + 0, s0), cf(t0 + 0, s0 + 1), cf(t0 + 0, s0 + 2), cf(t0 + 0, s0 + 3));
-        v.y = tsx_to_fp8x4(cf(t0 + 1, s0), cf(t0 + 1, s0 + 1), cf(t0 + 1, s0 + 2), cf(t0 + 1, s0 + 3));
-        v.z = tsx_to_fp8x4(cf(t0 + 2, s0), cf(t0 + 2, s0 + 1), cf(t0 + 2, s0 + 2), cf(t0 + 2, s0 + 3));
-        v.w = tsx_to_fp8x4(cf(t0 + 3, s0), cf(t0 + 3, s0 + 1), cf(t0 + 3, s0 + 2), cf(t0 + 3, s0 + 3));
-      } else if (grp < 12 + TSX_S16H_BO) {  // side dst 8 + dd from the eight top sources
-        const int d = 8 + (grp - 4 - TSX_S16H_BO);
+      } else if (grp < 16) {  // side dst 8 + dd from the eight top sources
+        const int d = grp;
         v.x = tsx_to_h2(cf(d, 0), cf(d, 1));
         v.y = tsx_to_h2(cf(d, 2), cf(d, 3));
         v.z = tsx_to_h2(cf(d, 4), cf(d, 5));
         v.w = tsx_to_h2(cf(d, 6), cf(d, 7));
       } else {  // side dst from the side sources of the neighbouring columns
-        const int s0 = grp < 14 + TSX_S16H_BO ? 12 : 8, d0 = 8 + 4 * (grp & 1);
+        const int s0 = grp < 18 ? 12 : 8, d0 = 8 + 4 * (grp & 1);
         v.x = tsx_to_fp8x4(cf(d0 + 0, s0), cf(d0 + 0, s0 + 1), cf(d0 + 0, s0 + 2), cf(d0 + 0, s0 + 3));
         v.y = tsx_to_fp8x4(cf(d0 + 1, s0), cf(d0 + 1, s0 + 1), cf(d0 + 1, s0 + 2), cf(d0 + 1, s0 + 3));
         v.z = tsx_to_fp8x4(cf(d0 + 2, s0), cf(d0 + 2, s0 + 1), cf(d0 + 2, s0 + 2), cf(d0 + 2, s0 + 3));
@@ -1605,17 +1471,8 @@ __device__ __forceinline__ TsxM4 tsx_mm4(const TsxH4 &X, const TsxM4 &Y) {
   return O;
 }
 
-#ifndef TSX_PCSH_KEEP_E
-#define TSX_PCSH_KEEP_E 1  // E of a thread's levels stays in registers between the two upward phases (0: loaded again)
-#endif
-#ifndef TSX_PCSH_KEEP_GT
-#define TSX_PCSH_KEEP_GT 1  // likewise GT between the two downward phases
-#endif
-#ifndef TSX_PCSH_WAVES
-#define TSX_PCSH_WAVES 2
-#endif
 template <int LSEG, int NSEG, int CW, bool GS, int MODE, bool IDX = false, int RQ = 0>
-__global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG == 2 ? 3 : TSX_PCSH_WAVES, LSEG == 2 ? 3 : TSX_PCSH_WAVES))) void tsx_k_pcsh_rb(TsxGeo g, const uint4 *__restrict__ P, const uint4 *__restrict__ PB,
+__global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(2, 2))) void tsx_k_pcsh_rb(TsxGeo g, const uint4 *__restrict__ P, const uint4 *__restrict__ PB,
                                                           long long bstride, const int *__restrict__ cidx,
                                                           const float *__restrict__ r, float *__restrict__ z,
                                                           unsigned *__restrict__ zb, float *__restrict__ zfin,
@@ -1731,13 +1588,11 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
   };
 
   // ---- phase 1: local upward scan with zero inflow; keeps beta, rd + couplings and E of its levels
-  // (E and GT of a level are loaded again where the re-run needs them -- L2 hits -- instead of being held: 32 registers
-  // per level would halve the occupancy)
   float beta[LSEG][4], rdg[LSEG][4];
   uint2 nb[LSEG][4];
   unsigned eid[LSEG];
   unsigned pr[LSEG];  // row of the level's recurrence records (the cell, or its entry of the shared table)
-  TsxH4 Ekeep[TSX_PCSH_KEEP_E ? LSEG : 1];  // E of the levels, held for the re-run of phase 2 (8 registers per level as fp16)
+  TsxH4 Ekeep[LSEG];  // E of the levels, held for the re-run of phase 2 (8 registers per level as fp16)
   // (the levels' indices first and the wave-uniform decisions -- shared records or not, rank faces or not -- outside the level
   // loop: a branch per level fences the levels' loads off from each other)
   if (pidx) {
@@ -1778,40 +1633,25 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
         nbr_load(halo, level(l), c, nb[l]);
         float zx[4], zy[4];
         nbr_vals(nb[l], zx, zy);
-        if (TSX_PCS_C16) {  // fp16: two top dsts per record; the y sources first, then the x sources (four records live at a time)
+        // fp16: two top dsts per record; the y sources first, then the x sources (four records live at a time)
 #pragma unroll
-          for (int ax = 0; ax < 2; ++ax) {
-            const float(&zz)[4] = ax == 0 ? zy : zx;
+        for (int ax = 0; ax < 2; ++ax) {
+          const float(&zz)[4] = ax == 0 ? zy : zx;
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-              const tsx_h8 hh = __builtin_bit_cast(tsx_h8, brec(4 * ax + m, c, eid[l]));
+          for (int m = 0; m < 4; ++m) {
+            const tsx_h8 hh = __builtin_bit_cast(tsx_h8, brec(4 * ax + m, c, eid[l]));
 #pragma unroll
-              for (int q = 0; q < 4; ++q) {  // top dst t = 2 m (not inward: up), t = 2 m + 1 (down)
-                ru[m] = __builtin_fmaf((float)hh[q], zz[q], ru[m]);
-                rd[m] = __builtin_fmaf((float)hh[4 + q], zz[q], rd[m]);
-              }
+            for (int q = 0; q < 4; ++q) {  // top dst t = 2 m (not inward: up), t = 2 m + 1 (down)
+              ru[m] = __builtin_fmaf((float)hh[q], zz[q], ru[m]);
+              rd[m] = __builtin_fmaf((float)hh[4 + q], zz[q], rd[m]);
             }
           }
-        } else {
-        const uint4 cy0 = brec(0, c, eid[l]), cy1 = brec(1, c, eid[l]), cx0 = brec(2, c, eid[l]), cx1 = brec(3, c, eid[l]);
-        const unsigned wy[8] = {cy0.x, cy0.y, cy0.z, cy0.w, cy1.x, cy1.y, cy1.z, cy1.w};
-        const unsigned wx[8] = {cx0.x, cx0.y, cx0.z, cx0.w, cx1.x, cx1.y, cx1.z, cx1.w};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          float cq[4], cp[4];
-          tsx_fp8x4(wy[t], cq);
-          tsx_fp8x4(wx[t], cp);
-          const float s8 = cq[0] * zy[0] + cq[1] * zy[1] + cq[2] * zy[2] + cq[3] * zy[3] + cp[0] * zx[0] + cp[1] * zx[1] +
-                           cp[2] * zx[2] + cp[3] * zx[3];
-          if (t & 1) rd[t >> 1] += s8 * (1.0f / TSX_FP8_SCALE);
-          else ru[t >> 1] += s8 * (1.0f / TSX_FP8_SCALE);
-        }
         }
       }
       float Fr[4];
       tsx_mv4(F, rd, Fr);
       const TsxH4 E = mat(0, pr[l]);
-      if (TSX_PCSH_KEEP_E) Ekeep[l] = E;
+      Ekeep[l] = E;
       float EB[4];
       tsx_mv4(E, Bl, EB);
       const TsxM4 EP = tsx_mm4(E, Pc);
@@ -1839,7 +1679,7 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
     float Bc[4] = {Bin[0], Bin[1], Bin[2], Bin[3]};
 #pragma unroll
     for (int l = LSEG - 1; l >= 0; --l) {
-      const TsxH4 E = TSX_PCSH_KEEP_E ? Ekeep[l] : mat(0, pr[l]);
+      const TsxH4 E = Ekeep[l];
       float EB[4];
       tsx_mv4(E, Bc, EB);
 #pragma unroll
@@ -1852,7 +1692,7 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
   __syncthreads();  // everybody has read the upward summaries: the buffer is free for the downward ones
   // ---- phase 3: local downward scan with zero inflow; keeps gamma and GT of its levels
   float gam[LSEG][4];
-  TsxH4 GTkeep[TSX_PCSH_KEEP_GT ? LSEG : 1];
+  TsxH4 GTkeep[LSEG];
   {
     float Vl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     TsxM4 Qc;
@@ -1865,7 +1705,7 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
       const bool act = l < nl;
       const TsxH4 G = mat(4, pr[l]), Hm = mat(6, pr[l]);  // (G stored minus the identity)
       const TsxH4 GT = mat(8, pr[l]);
-      if (TSX_PCSH_KEEP_GT) GTkeep[l] = GT;
+      GTkeep[l] = GT;
       float Bn[4], Gr[4], HB[4], GV[4];
 #pragma unroll
       for (int a = 0; a < 4; ++a) Bn[a] = l + 1 < LSEG ? Bk[l + 1 < LSEG ? l + 1 : l][a] : Bin[a];
@@ -1902,13 +1742,12 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
   }
   for (int s2 = 0; s2 < sg; ++s2) chain(s2, V);
   // ---- phase 4: true V, U; side streams; stores
-  unsigned zw[(MODE == 0 && TSX_PCSH_DEFER_ST) ? LSEG : 1][4];
 #pragma unroll
   for (int l = 0; l < LSEG; ++l) {
     const bool st = live && l < nl;
     const unsigned c = cell(l);
     const unsigned cn = (unsigned)level(l) * ncol + ncp;
-    const TsxH4 GT = TSX_PCSH_KEEP_GT ? GTkeep[l] : mat(8, pr[l]), An = mat(10, pr[l]);
+    const TsxH4 GT = GTkeep[l], An = mat(10, pr[l]);
     float Bn[4], GV[4], Vn[4], AV[4], Un[4], U[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) Bn[a] = l + 1 < LSEG ? Bk[l + 1 < LSEG ? l + 1 : l][a] : Bin[a];
@@ -1948,10 +1787,10 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
     uint4 sy[2], sx[2];
     if (GS) {
       nbr_vals(nb[l], zx, zy);
-      sy[0] = brec(12 + TSX_S16H_BO, c, eid[l]);
-      sy[1] = brec(13 + TSX_S16H_BO, c, eid[l]);
-      sx[0] = brec(14 + TSX_S16H_BO, c, eid[l]);
-      sx[1] = brec(15 + TSX_S16H_BO, c, eid[l]);
+      sy[0] = brec(16, c, eid[l]);
+      sy[1] = brec(17, c, eid[l]);
+      sx[0] = brec(18, c, eid[l]);
+      sx[1] = brec(19, c, eid[l]);
     }
     const unsigned uy[8] = {sy[0].x, sy[0].y, sy[0].z, sy[0].w, sy[1].x, sy[1].y, sy[1].z, sy[1].w};
     const unsigned ux[8] = {sx[0].x, sx[0].y, sx[0].z, sx[0].w, sx[1].x, sx[1].y, sx[1].z, sx[1].w};
@@ -1975,7 +1814,7 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
     float zo[8];
 #pragma unroll
     for (int dd = 0; dd < 8; ++dd) {
-      const tsx_h8 row = __builtin_bit_cast(tsx_h8, brec(4 + TSX_S16H_BO + dd, c, eid[l]));
+      const tsx_h8 row = __builtin_bit_cast(tsx_h8, brec(8 + dd, c, eid[l]));
       float acc = rs[dd];
 #pragma unroll
       for (int a = 0; a < 4; ++a) acc = __builtin_fmaf((float)row[2 * a + 1], V[a], __builtin_fmaf((float)row[2 * a], Un[a], acc));
@@ -1989,18 +1828,11 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
       zo[dd] = acc;
     }
     // records by consumer: side dofs (8,10) (9,11) (12,14) (13,15) = zo[0,2] zo[1,3] zo[4,6] zo[5,7]
-    if (MODE == 0) {
-      if (TSX_PCSH_DEFER_ST) {  // stored behind the level loop: no (predicated) store between the levels' loads
-        zw[l][0] = tsx_bf16x2(zo[0], zo[2]);
-        zw[l][1] = tsx_bf16x2(zo[1], zo[3]);
-        zw[l][2] = tsx_bf16x2(zo[4], zo[6]);
-        zw[l][3] = tsx_bf16x2(zo[5], zo[7]);
-      } else if (st) {
-        tsx_sto(zb, (size_t)0 * Nc, c, tsx_bf16x2(zo[0], zo[2]));
-        tsx_sto(zb, (size_t)1 * Nc, c, tsx_bf16x2(zo[1], zo[3]));
-        tsx_sto(zb, (size_t)2 * Nc, c, tsx_bf16x2(zo[4], zo[6]));
-        tsx_sto(zb, (size_t)3 * Nc, c, tsx_bf16x2(zo[5], zo[7]));
-      }
+    if (MODE == 0 && st) {
+      tsx_sto(zb, (size_t)0 * Nc, c, tsx_bf16x2(zo[0], zo[2]));
+      tsx_sto(zb, (size_t)1 * Nc, c, tsx_bf16x2(zo[1], zo[3]));
+      tsx_sto(zb, (size_t)2 * Nc, c, tsx_bf16x2(zo[4], zo[6]));
+      tsx_sto(zb, (size_t)3 * Nc, c, tsx_bf16x2(zo[5], zo[7]));
     }
     if (MODE == 1 && st) {
       tsx_sto(zr, (size_t)0 * Nc, c, make_float2(zo[0], zo[2]));
@@ -2024,14 +1856,5 @@ __global__ __launch_bounds__(CW *NSEG) __attribute__((amdgpu_waves_per_eu(LSEG =
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a) V[a] = l < nl ? Vn[a] : V[a];
-  }
-  if (MODE == 0 && TSX_PCSH_DEFER_ST) {
-#pragma unroll
-    for (int l = 0; l < LSEG; ++l) {
-      if (!(live && l < nl)) continue;
-      const unsigned c = cell(l);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) tsx_sto(zb, (size_t)m * Nc, c, zw[l][m]);
-    }
   }
 }

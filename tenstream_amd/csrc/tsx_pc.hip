@@ -23,16 +23,11 @@ static int pc_column_launch(tsx_solver *s, const double *v, ZT *z, const ZT *zy,
     if constexpr (NTOP == 2) {
       // sweep temporaries in LDS when a block's share (Nz x 64 columns x 16 B) fits the per-block limit
       const size_t lds = (size_t)g.Nz * 64 * sizeof(float4);
-      static int use_lds = -1;  // TSX_PC_LDS=0: keep them in global memory (A/B knob)
-      if (use_lds < 0) {
-        const char *e = getenv("TSX_PC_LDS");
-        use_lds = e ? atoi(e) : 1;
-      }
 #define TSX_P16_LAUNCH(HAS, LDST, BYTES)                                                                                        \
   hipLaunchKernelGGL((tsx_k_pc_column_p16<ROWS, GS, HAS, XL, LDST>), dim3(nb), dim3(64), BYTES, s->stream, g,                    \
                      (const uint4 *)s->coef_h, s->l1d, s->a11, s->a12, s->albedo, (const float *)s->pc_rhs, z, zy, zx,             \
                      (float4 *)s->pc_tmp, done)
-      if (use_lds && lds <= (size_t)s->max_lds) {
+      if (lds <= (size_t)s->max_lds) {
         if (s->any_l1d) TSX_P16_LAUNCH(true, true, lds);
         else TSX_P16_LAUNCH(false, true, lds);
       } else {
@@ -54,35 +49,27 @@ static int pc_column_launch(tsx_solver *s, const double *v, ZT *z, const ZT *zy,
     return TSX_OK;
   } else {
     // fp64 directions: the exact blocks
-    static int use_h1 = -1;  // TSX_PC_PREFETCH=0 selects the generic kernel for 3_10 as well (A/B knob)
-    if (use_h1 < 0) {
-      const char *e = getenv("TSX_PC_PREFETCH");
-      use_h1 = e ? atoi(e) : 1;
-    }
     if constexpr (NTOP == 2) {
-      if (use_h1) {
 #define TSX_H1_LAUNCH(CTYPE, HAS)                                                                                              \
   hipLaunchKernelGGL((tsx_k_pc_column_h1<CTYPE, ROWS, GS, ZT, HAS, XL>), dim3(nb), dim3(64), 0, s->stream, g,                     \
                      (const CTYPE *)s->coef, s->l1d, s->a11, s->a12, s->albedo, v, z, zy, zx, (void *)s->pc_tmp, done)
-        if (s->coef_bytes == 4) {
-          if (s->any_l1d) TSX_H1_LAUNCH(float, true);
-          else TSX_H1_LAUNCH(float, false);
-        } else {
-          if (s->any_l1d) TSX_H1_LAUNCH(double, true);
-          else TSX_H1_LAUNCH(double, false);
-        }
-#undef TSX_H1_LAUNCH
-        HIPCHK(hipGetLastError());
-        return TSX_OK;
+      if (s->coef_bytes == 4) {
+        if (s->any_l1d) TSX_H1_LAUNCH(float, true);
+        else TSX_H1_LAUNCH(float, false);
+      } else {
+        if (s->any_l1d) TSX_H1_LAUNCH(double, true);
+        else TSX_H1_LAUNCH(double, false);
       }
+#undef TSX_H1_LAUNCH
+    } else {
+      // generic kernel (8_16): y coupling only
+      if (s->coef_bytes == 4)
+        hipLaunchKernelGGL((tsx_k_pc_column<NTOP, NSIDE, float, ROWS, GS, ZT>), dim3(nb), dim3(64), 0, s->stream, g,
+                           (const float *)s->coef, s->l1d, s->a11, s->a12, s->albedo, v, z, zy, s->pc_tmp, done);
+      else
+        hipLaunchKernelGGL((tsx_k_pc_column<NTOP, NSIDE, double, ROWS, GS, ZT>), dim3(nb), dim3(64), 0, s->stream, g,
+                           (const double *)s->coef, s->l1d, s->a11, s->a12, s->albedo, v, z, zy, s->pc_tmp, done);
     }
-    // generic kernel (8_16, or A/B): y coupling only
-    if (s->coef_bytes == 4)
-      hipLaunchKernelGGL((tsx_k_pc_column<NTOP, NSIDE, float, ROWS, GS, ZT>), dim3(nb), dim3(64), 0, s->stream, g,
-                         (const float *)s->coef, s->l1d, s->a11, s->a12, s->albedo, v, z, zy, s->pc_tmp, done);
-    else
-      hipLaunchKernelGGL((tsx_k_pc_column<NTOP, NSIDE, double, ROWS, GS, ZT>), dim3(nb), dim3(64), 0, s->stream, g,
-                         (const double *)s->coef, s->l1d, s->a11, s->a12, s->albedo, v, z, zy, s->pc_tmp, done);
     HIPCHK(hipGetLastError());
     return TSX_OK;
   }
@@ -115,12 +102,7 @@ static int apply_pc(tsx_solver *s, const double *v, ZT *z, bool in_solve) {
       unsigned short *zb = (unsigned short *)(zs + (size_t)g.N);   // bf16 neighbour values of the intermediate passes
       const int nb = (g.ym * (g.xm / 2) + 63) / 64;
       const size_t lds = (size_t)g.Nz * 64 * sizeof(float4);
-      static int use_lds = -1;
-      if (use_lds < 0) {
-        const char *e = getenv("TSX_PC_LDS");
-        use_lds = e ? atoi(e) : 1;
-      }
-      const bool ld = NTOP == 2 && use_lds && lds <= (size_t)s->max_lds;
+      const bool ld = NTOP == 2 && lds <= (size_t)s->max_lds;
       // 3_10: pass modes 0 (intermediate: bf16 side streams only), 1 (first colour's last pass: fp32), 2 (last pass: pairs).
       // 8_16 keeps fp32 iterates throughout: its kernel knows FINAL (= mode 2) only.
 #define TSX_RB_LAUNCH(GSV, HAS, LDSV, MODEV)                                                                                    \

@@ -12,7 +12,7 @@ struct PcsCfg {
 };
 
 // (LSEG, NSEG) pairs that are instantiated; CW in {64, 32, 16}
-static const int k_pairs[][2] = {{4, 16}, {8, 8}, {8, 16}, {16, 16}, {2, 32}};  // (2, 32): 8_16 only, A/B (round 6)
+static const int k_pairs[][2] = {{4, 16}, {8, 8}, {8, 16}, {16, 16}};
 
 static PcsCfg pcs_config(const tsx_solver *s) {
   const TsxGeo &g = s->geo;
@@ -37,13 +37,9 @@ static PcsCfg pcs_config(const tsx_solver *s) {
     }
     if (c.lseg == 16 || (c.lseg == 8 && c.nseg == 8)) c.lseg = c.nseg = 0;  // not instantiated for 8_16
     if (!c.lseg) return c;
-    // two levels per thread (TSX_PCS_CFG=2,32,8|16): half the per-level state in registers -- three workgroups of 8 columns x 32
-    // segments per CU instead of one of 32 x 16 (round 6 A/B, profiles/r06)
-    if (c.lseg == 2) c.cw = e_cw == 16 ? 16 : 8;
-    else c.cw = (e_cw == 32 || e_cw == 16) ? e_cw : (nthr >= 8192 ? 32 : 16);
+    c.cw = (e_cw == 32 || e_cw == 16) ? e_cw : (nthr >= 8192 ? 32 : 16);
     return c;
   }
-  if (c.lseg == 2) c.lseg = c.nseg = 0;  // 3_10: not instantiated
   if (!c.lseg) {
     // measured (scripts/pcsbench.py): 8 levels x 8 segments on large passes (>= 16 K columns: fewer, fatter threads),
     // 4 x 16 on small ones (more waves); deeper columns take the smallest pair that holds them
@@ -64,22 +60,14 @@ static PcsCfg pcs_config(const tsx_solver *s) {
   return c;
 }
 
-// side -> top couplings (record 1) as two fp16 records instead of one fp8 record (tsx_kernels_pcs.hpp "C16"): a build-time
-// choice (both variants of every pass kernel would double the compile time); measured 6 -> 5 iterations on the metric domain
-#ifndef TSX_PCS_C16
-#define TSX_PCS_C16 1
-#endif
-static constexpr bool pcs_c16() { return TSX_PCS_C16 != 0; }
-
 bool tsx_pcs_eligible(const tsx_solver *s) {
   const char *e = getenv("TSX_PC_SCAN");  // TSX_PC_SCAN=0: the one-lane-per-column kernels (A/B knob)
   const int on = e ? atoi(e) : 1;
   return on && pcs_config(s).lseg > 0;
 }
 
-static int pcsh_pack(tsx_solver *s) {  // 8_16: 14 matrix records per cell, then 16 / 20 block records per cell or per entry
+static int pcsh_pack(tsx_solver *s) {  // 8_16: 14 matrix records per cell, then 20 block records per cell or per entry
   const TsxGeo &g = s->geo;
-  s->coef_h_c16 = pcs_c16();
   uint4 *P = (uint4 *)s->coef_h, *PB = P + (size_t)TSX_S16H_CELL * g.Nc;
   s->coef_h_dd = false;
   const int nbc = (g.ncol + 63) / 64;
@@ -121,19 +109,15 @@ int tsx_pcs_pack(tsx_solver *s) {
     else
       hipLaunchKernelGGL((tsx_k_pcs_pack_col<float>), dim3((g.ncol + 63) / 64), dim3(64), 0, s->stream, g, (const float *)s->coef,
                          s->l1d, s->a11, s->a12, s->albedo, P, (const int *)nullptr, 0ll);
-    s->coef_h_c16 = pcs_c16();
     // near-identical grouping (dd_pc without dd_on): a wave's ids are unrelated -> an entry's records in one line (TSX_PC_ENTRY_MAJOR=0 / 1 overrides)
     {
       const char *e = getenv("TSX_PC_ENTRY_MAJOR");
-      s->pe_entry_major = pcs_c16() && (e ? atoi(e) != 0 : (s->dd_pc && !s->dd_on));
+      s->pe_entry_major = e ? atoi(e) != 0 : (s->dd_pc && !s->dd_on);
     }
-    if (s->coef_h_c16)  // side -> top couplings in fp16: 8 records per distinct block
-      hipLaunchKernelGGL(tsx_k_pcs_pack_ent16, dim3(grid_for((long long)TSX_PCS_ENT16_SLOTS * s->pc_nent)), dim3(TSX_BLOCK), 0,
-                         s->stream, g.ncol, (long long)s->pc_nent, (const float *)s->pc_coef, (const int *)s->pc_ent_cell, s->l1d,
-                         P + g.Nc, s->pe_entry_major ? 1 : 0);
-    else
-      hipLaunchKernelGGL(tsx_k_pcs_pack_ent, dim3(grid_for(7ll * s->pc_nent)), dim3(TSX_BLOCK), 0, s->stream, g.ncol,
-                         (long long)s->pc_nent, (const float *)s->pc_coef, (const int *)s->pc_ent_cell, s->l1d, P + g.Nc);
+    // side -> top couplings in fp16: 8 records per distinct block
+    hipLaunchKernelGGL(tsx_k_pcs_pack_ent16, dim3(grid_for((long long)TSX_PCS_ENT16_SLOTS * s->pc_nent)), dim3(TSX_BLOCK), 0,
+                       s->stream, g.ncol, (long long)s->pc_nent, (const float *)s->pc_coef, (const int *)s->pc_ent_cell, s->l1d,
+                       P + g.Nc, s->pe_entry_major ? 1 : 0);
     // the intermediate passes' copy of record 0 (block index in the word of A_k) in the last group's slot: the entries
     // fill at most 3.5 of the 7 groups behind record 0 (sharing is on only where 2 * nent <= Nc)
     hipLaunchKernelGGL(tsx_k_pcs_pack_r0g, dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, (long long)g.Nc, (const uint4 *)P,
@@ -146,23 +130,20 @@ int tsx_pcs_pack(tsx_solver *s) {
     if ((long long)g.ym * (g.xm / 2) < 16384) return TSX_OK;
     return tsx_records_share(s, 1, P + (size_t)7 * g.Nc);
   }
-  s->coef_h_c16 = pcs_c16();
   if (s->coef_bytes == 4) {
     hipLaunchKernelGGL((tsx_k_pcs_pack_col<float>), dim3((g.ncol + 63) / 64), dim3(64), 0, s->stream, g, (const float *)s->coef,
                        s->l1d, s->a11, s->a12, s->albedo, P);
     hipLaunchKernelGGL((tsx_k_pcs_pack<float>), dim3(grid_for(7 * g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g, (const float *)s->coef,
                        s->l1d, P);
-    if (s->coef_h_c16)
-      hipLaunchKernelGGL((tsx_k_pcs_pack_rec1h<float>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
-                         (const float *)s->coef, s->l1d, P);
+    hipLaunchKernelGGL((tsx_k_pcs_pack_rec1h<float>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
+                       (const float *)s->coef, s->l1d, P);
   } else {
     hipLaunchKernelGGL((tsx_k_pcs_pack_col<double>), dim3((g.ncol + 63) / 64), dim3(64), 0, s->stream, g, (const double *)s->coef,
                        s->l1d, s->a11, s->a12, s->albedo, P);
     hipLaunchKernelGGL((tsx_k_pcs_pack<double>), dim3(grid_for(7 * g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
                        (const double *)s->coef, s->l1d, P);
-    if (s->coef_h_c16)
-      hipLaunchKernelGGL((tsx_k_pcs_pack_rec1h<double>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
-                         (const double *)s->coef, s->l1d, P);
+    hipLaunchKernelGGL((tsx_k_pcs_pack_rec1h<double>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
+                       (const double *)s->coef, s->l1d, P);
   }
   HIPCHK(hipGetLastError());
   return TSX_OK;
@@ -336,7 +317,6 @@ static void pcs_launch(tsx_solver *s, bool gs, int mode, int rbc, int nonbr, flo
   unsigned *rb = zb + (size_t)4 * g.Nc;  // behind the iterate's bf16 records in s->vw
   const int *pidx = dd && s->pcr_on ? (const int *)s->pcr_idx : (const int *)nullptr;  // shared record 0 of the intermediate passes
   const uint4 *PT = (const uint4 *)s->pcr_tab;
-  constexpr bool C16 = pcs_c16();
   // the pass stores its boundary records into the neighbours' mailboxes itself (tsx_pcs_apply decided; kernels instantiated
   // for the default configurations only, pcs_peer_kernel_ok)
   constexpr bool PEEROK = L == 4 && S == 16 && (CW == 16 || CW == 32);
@@ -345,7 +325,7 @@ static void pcs_launch(tsx_solver *s, bool gs, int mode, int rbc, int nonbr, flo
   if (peer) snd = s->pch_snd;
   else memset((void *)&snd, 0, sizeof(snd));
 #define TSX_PCS_GO1(GSV, MODEV, RQV, IDXV, PEERV)                                                                                \
-  hipLaunchKernelGGL((tsx_k_pcs_rb<L, S, CW, GSV, MODEV, IDXV, RQV, C16, PEERV>), dim3(nb), dim3(CW *S), 0, s->stream, g, P, r,  \
+  hipLaunchKernelGGL((tsx_k_pcs_rb<L, S, CW, GSV, MODEV, IDXV, RQV, PEERV>), dim3(nb), dim3(CW *S), 0, s->stream, g, P, r,       \
                      zs, zb, zfin, done, rbc, nonbr, IDXV ? cidx : (const int *)nullptr, IDXV ? nent : 0ll,                      \
                      IDXV ? PE : (const uint4 *)nullptr, hal, rb, part, IDXV ? pidx : (const int *)nullptr,                      \
                      IDXV ? PT : (const uint4 *)nullptr, snd, (IDXV && s->pe_entry_major) ? TSX_PCS_ENT16_SLOTS : 1)
@@ -423,18 +403,13 @@ static void pcsh_launch(tsx_solver *s, bool gs, int mode, int rbc, int nonbr, fl
 }
 
 // one pass: mode as in tsx_k_pcs_rb; first = no neighbour values exist yet
-// intermediate passes read their right-hand side as bf16 pairs (TSX_PC_RHS16=0: fp32 throughout).  Measured: 3_10 pass
-// 43.6 -> 36.5 us; 8_16 pass 168 -> 162 us, which pays from about 14 passes on (the two passes that leave the words cost what
-// four reading passes save); same iteration counts
+// intermediate passes read their right-hand side as bf16 pairs.  Measured: 3_10 pass 43.6 -> 36.5 us; 8_16 pass 168 -> 162 us,
+// which pays from about 14 passes on (the two passes that leave the words cost what four reading passes save); same iteration
+// counts
 // where the passes keep the bf16-pair words of their right-hand side (behind the iterate's records in s->vw)
 unsigned *tsx_pcs_words(const tsx_solver *s) {
   float *zs = (float *)s->vw;
   return (unsigned *)(zs + (size_t)s->geo.N) + (size_t)4 * s->geo.Nc;
-}
-bool tsx_pcs_rhs16(const tsx_solver *s) {
-  static const bool on = !(getenv("TSX_PC_RHS16") && atoi(getenv("TSX_PC_RHS16")) == 0);
-  (void)s;
-  return on;
 }
 
 // rq: right-hand side of an intermediate pass, see tsx_k_pcs_rb (RQ)
@@ -447,9 +422,7 @@ int tsx_pcs_pass(tsx_solver *s, int pass, int mode, float *zfin, const int *done
     const bool first8 = pass == 0, gs8 = !(first8 && mode == 0);
     const int nonbr8 = first8 && mode != 0, rbc8 = pass & 1;
     if (mode != 0) rq = 0;
-    if (c.lseg == 2 && c.cw == 16) pcsh_launch<2, 32, 16>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
-    else if (c.lseg == 2) pcsh_launch<2, 32, 8>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
-    else if (c.lseg == 4 && c.cw == 32) pcsh_launch<4, 16, 32>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
+    if (c.lseg == 4 && c.cw == 32) pcsh_launch<4, 16, 32>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
     else if (c.lseg == 4) pcsh_launch<4, 16, 16>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
     else if (c.cw == 32) pcsh_launch<8, 16, 32>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
     else pcsh_launch<8, 16, 16>(s, gs8, mode, rbc8, nonbr8, zs8, zb8, zfin, done, rq, part);
@@ -477,9 +450,8 @@ int tsx_pcs_apply(tsx_solver *s, float *z, const int *done) {
     int rc = pcs_halo_buffers(s);
     if (rc) return rc;
   }
-  const bool rhs16 = tsx_pcs_rhs16(s);
   // the producer of the right-hand side has left the bf16-pair words already (fp32 Krylov vectors, tsx_k_psupdate_k32c)
-  const bool words_ready = rhs16 && s->pc_words_ready && P >= 6;
+  const bool words_ready = s->pc_words_ready && P >= 6;
   s->pc_words_ready = false;
   static const int every_env = getenv("TSX_PC_HALO_EVERY") ? atoi(getenv("TSX_PC_HALO_EVERY")) : 1;
   const int every = every_env > 0 ? every_env : 1;
@@ -521,7 +493,7 @@ int tsx_pcs_apply(tsx_solver *s, float *z, const int *done) {
     }
     // a colour's intermediate visits are passes c, c + 2, ... < P - 2: the first leaves the bf16 right-hand side if another
     // one follows, the later ones read it
-    const int rq = !rhs16 || mode != 0 ? 0 : (words_ready ? 2 : (pass >= 2 ? 2 : (pass + 2 < P - 2 ? 1 : 0)));
+    const int rq = mode != 0 ? 0 : (words_ready ? 2 : (pass >= 2 ? 2 : (pass + 2 < P - 2 ? 1 : 0)));
     int rc;
     // peer transport, default configuration: the pass sends its boundary records itself (TSX_PEER_INPLACE=2, the default)
     const bool xchg_after = halo && pass + 1 < P && pass % every == 0;

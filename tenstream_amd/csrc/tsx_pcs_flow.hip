@@ -12,10 +12,6 @@
 #include "tsx_peer_dev.hpp"
 #include "tsx_kernels_pcs.hpp"
 
-#ifndef TSX_PCS_C16
-#define TSX_PCS_C16 1
-#endif
-
 static int flow_env() {
   const char *e = getenv("TSX_PC_FLOW");  // 0: a launch per pass (A/B knob, and what the parity test compares with); read per call
   return e ? atoi(e) : 1;
@@ -23,7 +19,7 @@ static int flow_env() {
 
 template <int CW, bool IDX, bool FAT>
 static const void *flow_kernel() {
-  return (const void *)tsx_k_pcs_flow<4, 16, CW, IDX, TSX_PCS_C16 != 0, FAT, false>;
+  return (const void *)tsx_k_pcs_flow<4, 16, CW, IDX, FAT, false>;
 }
 
 // resident workgroups of the flow kernel on this device.  Only a bound on the useful grid: tickets make any grid correct.
@@ -57,7 +53,6 @@ bool tsx_pcs_flow_ok(tsx_solver *s, int lseg, int nseg, int cw, bool faces) {
   if (g.pc_tile_x > 0 || g.pc_tile_y > 0) return false;
   const int h = g.xm >> 1;
   if (h % cw != 0) return false;  // a tile is CW columns of ONE row
-  if (!tsx_pcs_rhs16(s)) return false;
   if (faces) {
     if (getenv("TSX_FLOW_PEER") && atoi(getenv("TSX_FLOW_PEER")) == 0) return false;  // A/B: the passes as launches on several ranks
     if (g.ym % 2 != 0) return false;
@@ -67,9 +62,8 @@ bool tsx_pcs_flow_ok(tsx_solver *s, int lseg, int nseg, int cw, bool faces) {
     // per SIMD, the face columns send after the scan; bit-identical, tests force it with TSX_FLOW_FAT=0): 256 x 128 8.76 -> 10.58,
     // 128 x 256 8.58 -> 10.57, 256 x 256 15.98 -> 18.17 ms (profiles/r06/flow_peer_lean_ab.txt) -- a workgroup there runs ~25 items
     // one after the other, and every face item carries the drain of its uncached stores and the tag round trip on its own back.
-    // TSX_FLOW_PEER_LEAN=1 switches the lean variant on up to two tiles per resident workgroup, TSX_FLOW_PEER_ANY=1 lifts every bound
+    // TSX_FLOW_PEER_LEAN=1 switches the lean variant on up to two tiles per resident workgroup
     const long long nt = (long long)(h / cw) * g.ym;
-    if (getenv("TSX_FLOW_PEER_ANY") && atoi(getenv("TSX_FLOW_PEER_ANY"))) return true;
     if (nt <= flow_capacity(s, cw, true)) return true;
     if (!(getenv("TSX_FLOW_PEER_LEAN") && atoi(getenv("TSX_FLOW_PEER_LEAN")) != 0)) return false;
     return nt <= 2ll * flow_capacity(s, cw, false);
@@ -191,27 +185,20 @@ static int flow_launch(tsx_solver *s, int p0, int p1, const int *done, bool face
     if (co > 1) cap = cap / co > 1 ? cap / co : 1;
   }
   if (grid > cap) grid = cap;
-  if (const char *e = getenv("TSX_FLOW_GRID")) {
-    const int v = atoi(e);
-    if (v > 0) grid = v;
-  }
   const long long nitems = (long long)(p1 - p0) * ntiles;
   if (grid > nitems) grid = nitems;
-  constexpr bool C16 = TSX_PCS_C16 != 0;
   // granules (the records as their own flags, TsxGran) only where most workgroups would otherwise idle: the workgroups ahead of the
   // wave front spin on their sixteen 8-byte loads per lane, which slows a chip whose every workgroup has work.  Measured per solve
   // (gpurun_out/flow_matrix_1.txt -> profiles/r05): 64 x 64 columns, 128 tiles of 16 columns: 1.86 ms with progress words, 1.71 with
   // granules; 128 x 64, 128 tiles of 32: 2.51 / 2.51; 128 x 128, 256 tiles of 32 on 256 workgroups: 3.64 / 4.37.
-  bool gran = fat && 4 * ntiles <= cap_fat;
-  if (const char *e = getenv("TSX_FLOW_GRAN")) gran = fat && atoi(e) != 0;
-  if (faces) gran = false;
+  const bool gran = fat && 4 * ntiles <= cap_fat && !faces;
 #define TSX_FLOW_GO(IDXV, FATV, GRV)                                                                                               \
-  hipLaunchKernelGGL((tsx_k_pcs_flow<4, 16, CW, IDXV, C16, FATV, GRV>), dim3((unsigned)grid), dim3(CW * 16), 0, s->stream, g, P, r, zb, \
+  hipLaunchKernelGGL((tsx_k_pcs_flow<4, 16, CW, IDXV, FATV, GRV>), dim3((unsigned)grid), dim3(CW * 16), 0, s->stream, g, P, r, zb, \
                      done, IDXV ? cidx : (const int *)nullptr, IDXV ? nent : 0ll, IDXV ? PE : (const uint4 *)nullptr, rb,          \
                      IDXV ? pidx : (const int *)nullptr, IDXV ? PT : (const uint4 *)nullptr,                                       \
                      (IDXV && s->pe_entry_major) ? TSX_PCS_ENT16_SLOTS : 1, f)
 #define TSX_FLOW_GOP(IDXV, FATV)                                                                                                    \
-  hipLaunchKernelGGL((tsx_k_pcs_flow<4, 16, CW, IDXV, C16, FATV, false, true>), dim3((unsigned)grid), dim3(CW * 16), 0, s->stream, g, P, \
+  hipLaunchKernelGGL((tsx_k_pcs_flow<4, 16, CW, IDXV, FATV, false, true>), dim3((unsigned)grid), dim3(CW * 16), 0, s->stream, g, P, \
                      r, zb, done, IDXV ? cidx : (const int *)nullptr, IDXV ? nent : 0ll, IDXV ? PE : (const uint4 *)nullptr, rb,   \
                      IDXV ? pidx : (const int *)nullptr, IDXV ? PT : (const uint4 *)nullptr,                                       \
                      (IDXV && s->pe_entry_major) ? TSX_PCS_ENT16_SLOTS : 1, f)
@@ -245,15 +232,5 @@ int tsx_pcs_flow(tsx_solver *s, int cw, int p0, int p1, const int *done, bool fa
   if (p1 <= p0) return TSX_OK;
   return cw == 32 ? flow_launch<32>(s, p0, p1, done, faces) : flow_launch<16>(s, p0, p1, done, faces);
 }
-
-#ifdef TSX_FLOW_TRACE
-// analysis builds only: the stamps of the last flow launch(es), n items of 12 words
-extern "C" int tsx_debug_flow_trace(unsigned long long *out, int n) {
-  if (n > TSX_FLOW_TL_N) n = TSX_FLOW_TL_N;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(tsx_flow_tl), sizeof(unsigned long long) * 12 * (size_t)n));
-  return TSX_OK;
-}
-#endif
 
 TSX_CODE_PROBE(pcsflow)  // tsx_host.hpp: this unit's code object as it sits in device memory (diagnostics)

@@ -282,11 +282,9 @@ __global__ __launch_bounds__(PCX_CW *PCX_NSEG) void tsx_k_pcx_rb(TsxGeo g, const
 }  // namespace
 
 // exact scan passes available for this solver's grid?  (3_10, an even number of columns per row, an even number of rows where
-// the rank wraps onto itself in y, at most 256 levels); TSX_PC_EXACT_SCAN=0 keeps the zebra rows (A/B)
+// the rank wraps onto itself in y, at most 256 levels); elsewhere the zebra rows
 bool tsx_pcx_eligible(const tsx_solver *s) {
   const TsxGeo &g = s->geo;
-  const char *e = getenv("TSX_PC_EXACT_SCAN");
-  if (e && atoi(e) == 0) return false;
   return g.ntop == 2 && g.xm % 2 == 0 && g.xm >= 2 && (!g.wrap_y || g.ym % 2 == 0) && g.Nz <= 16 * PCX_NSEG && g.Nc < (1ll << 31);
 }
 

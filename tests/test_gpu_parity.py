@@ -777,7 +777,7 @@ def test_scan_preconditioner_equals_the_column_sweep(gpu, monkeypatch, Nx, Ny, N
     for a, b in zip(out["0"], out["1"]):   # the sweep rounds the side -> top couplings to fp8 (2^-4), the scan to fp16
         assert np.abs(a - b).max() <= 6e-2 * np.abs(a).max()
     # tight solves: a few dozen iterations.  The scan never needs more than the sweep; it may need fewer: it keeps the side ->
-    # top couplings in fp16 (tsx_kernels_pcs.hpp C16), the sweep kernels in fp8
+    # top couplings in fp16 (tsx_k_pcs_pack_rec1h), the sweep kernels in fp8
     assert out["its1"] <= out["its0"] + max(1, round(0.1 * out["its0"])) and out["its1"] >= 0.6 * out["its0"], (out["its0"], out["its1"])
     assert np.abs(out["x0"] - out["x1"]).max() <= 1e-8 * np.abs(out["x0"]).max()
     # against the model: red-black Gauss-Seidel on the exact column blocks, 5 passes
