@@ -404,6 +404,17 @@ int tsx_log_get(tsx_solver *s, int32_t *nevents, const char **names, int64_t *co
  * spent in quarantine}.  device < 0: the current device.  The reference allocates its coefficient arrays once per solver
  * (alloc_coeff_diff2diff, src/pprts.F90:3396-3490); here no driver allocation lies on a solver's path after the first set. */
 int tsx_pool_stats(int device, int64_t *out8);
+/* hostile-memory mode of the pool: with TSX_POOL_POISON=<byte> (read on every call) every piece taken or freed is filled with the byte,
+ * and every piece taken gets red zones of 4 KiB in front and 4 KiB + its rounding slack behind; tsx_dev_free checks a piece's zones.
+ * out4 = {live pieces with red zones checked now, damaged zones found now + found at free since the last reset, requested bytes of
+ * the first damaged piece, offset of its first damaged byte from the end of the requested bytes (negative: the front zone)}; reset != 0
+ * clears the findings at free.  TSX_POOL_VERBOSE prints each finding to stderr.  device < 0: the current device.  No reference
+ * counterpart (round 5's test-only hipMalloc interposer did this by hand). */
+int tsx_pool_check(int device, int reset, int64_t *out4);
+/* the detector's self test: takes a piece of `bytes` with red zones (TSX_POOL_POISON must be set), writes `nbytes` bytes at `off` from
+ * the end of the requested bytes -- refused unless they lie inside that piece's own zones --, fills out4 as tsx_pool_check (no reset)
+ * would while the piece is live, then frees it (the free records the damage too).  No reference counterpart. */
+int tsx_pool_debug_overrun(int64_t bytes, int64_t off, int64_t nbytes, int64_t *out4);
 
 /* diagnostics: the code of one of libtsx's eight device code objects AS IT SITS IN DEVICE MEMORY (unit 0..7 = api, spmv310, spmv816,
  * pc, pcs, pcsflow, dedup, peer).  The unit's probe kernel reports its program counter in *pc_out and copies nwords 32-bit words from

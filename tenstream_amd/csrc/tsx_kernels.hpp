@@ -636,7 +636,10 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_lut_diff2diff(TsxGeo g, TsxLu
     const long long t = c / xm;
     const int j = (int)(t % ym);
     const int k = (int)(t / ym);
-    if (l1d[k]) {
+    if (l1d[k]) {  // no block in a 1-D layer: zeros, as the shared storage's 1-D entry holds (the operator never reads them; the
+                   // export does -- the planes come from the pool and may hold anything)
+#pragma unroll
+      for (int q = 0; q < DD; ++q) C[(size_t)q * Nc + c] = 0.0f;
       if (hash) hash[c] = TSX_DD_H1D;
       continue;
     }

@@ -80,7 +80,11 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_lut_dir(TsxGeo g, TsxLutDev L
     const long long t = c / xm;
     const int j = (int)(t % ym);
     const int k = (int)(t / ym);
-    if (l1d[k]) continue;
+    if (l1d[k]) {  // no block in a 1-D layer: zeros (the sweeps never read them; the export does, and pool memory may hold anything)
+#pragma unroll
+      for (int q = 0; q < NV; ++q) C[(size_t)q * Nc + c] = 0.0f;
+      continue;
+    }
     float aspect, w0, tauz, gcell;
     if (samp) {  // the cells' LUT coordinates in cell order (tsx_k_cell_samples)
       const float4 v = samp[c];

@@ -19,6 +19,13 @@
 //     set no driver allocation lies on a solver's path at all (the reference allocates its coefficient arrays once per solver
 //     too, alloc_coeff_diff2diff, src/pprts.F90:3396-3490) -- which also takes hipMalloc / hipFree off config 4's per-g-point path.
 // tsx_dev_free keeps hipFree's contract: it synchronises the device first (callers free scratch that queued kernels still read).
+//
+// Hostile-memory mode (TSX_POOL_POISON=<byte>, read on every call).  A piece handed out again keeps what its
+// last user left in it, and a write a few bytes past a buffer lands in rounding slack or a neighbour without a sound.  With the
+// variable set every piece taken is filled with the byte (0xFF: NaN in every float format, -1 as an integer), every piece freed is
+// filled with it again, and every piece taken gets red zones (kZone bytes in front, the rounding slack + kZone behind) filled with
+// 0xA5 (0x5A if that is the poison byte: change the byte only while no zoned piece is live); tsx_dev_free and tsx_pool_check report
+// damaged zones.  Unset: nothing of this runs and no piece is larger.
 #include <stdio.h>
 #include <unistd.h>
 
@@ -34,6 +41,7 @@
 namespace {
 constexpr unsigned kPattern = 0xA5C3F00Du;
 constexpr size_t kAlign = TsxPieceMap::kAlign;
+constexpr size_t kZone = TsxPieceMap::kZone;
 
 __global__ __launch_bounds__(256) void tsx_k_pool_fill(unsigned *p, size_t nwords, unsigned v) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (size_t)gridDim.x * 256) p[i] = v;
@@ -51,13 +59,34 @@ __global__ __launch_bounds__(256) void tsx_k_pool_verify(const unsigned *p, size
     atomicMin(&out[1], first);
   }
 }
+// `n` bytes from a word-aligned `p` := b (words, then the tail of fewer than four bytes)
+__global__ __launch_bounds__(256) void tsx_k_pool_fill_bytes(unsigned char *p, size_t n, unsigned char b) {
+  const size_t nw = n / 4;
+  const unsigned v = 0x01010101u * b;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nw; i += (size_t)gridDim.x * 256) ((unsigned *)p)[i] = v;
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) p[nw * 4 + threadIdx.x] = b;
+}
+// the same count as tsx_k_pool_verify, byte by byte (a red zone starts wherever the caller's bytes end)
+__global__ __launch_bounds__(256) void tsx_k_pool_verify_bytes(const unsigned char *p, size_t n, unsigned char b, unsigned long long *out) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    if (p[i] != b) {
+      bad++;
+      if (i < first) first = i;
+    }
+  if (bad) {
+    atomicAdd(&out[0], bad);
+    atomicMin(&out[1], first);
+  }
+}
 
 struct Pool {
   std::mutex mu;
   TsxPieceMap m;  // every byte of every slab belongs to exactly one piece (tsx_pool_map.hpp)
-  unsigned long long *flag = nullptr;  // [2] device words of the verify kernel
+  unsigned long long *flag = nullptr;  // [2] device words of the verify kernel; [2..5] the two red zones of one piece
   hipStream_t st = nullptr;            // the NULL stream, synchronised as a stream (never the device): see pool_tools
   long long wipes = 0, wiped_words = 0, first_wipe_us = -1, driver_allocs = 0, guard_us_spent = 0;
+  long long zones_bad_at_free = 0, first_bad_user = 0, first_bad_off = 0;  // red zones found damaged by tsx_dev_free since the last reset
 };
 std::mutex g_mu;
 std::map<int, Pool *> g_pools;
@@ -93,8 +122,38 @@ int grid_of(size_t nwords) {
 hipError_t pool_tools(Pool *P) {
   hipError_t e = hipSuccess;
   // the verify kernel's two result words: pinned host memory (nothing the platform clears behind our back)
-  if (!P->flag && (e = hipHostMalloc((void **)&P->flag, 2 * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess) return e;
+  if (!P->flag && (e = hipHostMalloc((void **)&P->flag, 6 * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess) return e;
   return e;
+}
+
+// TSX_POOL_POISON: the byte, or -1 (unset)
+int poison_byte() {
+  const char *e = getenv("TSX_POOL_POISON");
+  return e && *e ? (int)(strtol(e, nullptr, 0) & 0xff) : -1;
+}
+// the red zones' byte: never the poison byte
+unsigned char zone_byte(int poison) { return poison == 0xA5 ? 0x5A : 0xA5; }
+void fill(Pool *P, void *p, size_t n, unsigned char b) {
+  hipLaunchKernelGGL(tsx_k_pool_fill_bytes, dim3(grid_of(n / 4)), dim3(256), 0, P->st, (unsigned char *)p, n, b);
+}
+// the red zones of one live zoned piece: -> how many are damaged (0..2); *off = offset of the lowest damaged byte from the user end
+int check_zones(Pool *P, const std::pair<char *const, TsxPiece> &kv, long long *off) {
+  const char *u = kv.first + kZone, *ue = u + kv.second.user, *end = kv.first + kv.second.bytes;
+  const unsigned char zb = zone_byte(poison_byte());
+  unsigned long long *f = P->flag + 2;
+  f[0] = f[2] = 0;
+  f[1] = f[3] = ~0ull;
+  hipLaunchKernelGGL(tsx_k_pool_verify_bytes, dim3(grid_of(kZone / 4)), dim3(256), 0, P->st, (const unsigned char *)kv.first, kZone, zb, f);
+  hipLaunchKernelGGL(tsx_k_pool_verify_bytes, dim3(grid_of((size_t)(end - ue) / 4)), dim3(256), 0, P->st, (const unsigned char *)ue,
+                     (size_t)(end - ue), zb, f + 2);
+  if (hipStreamSynchronize(P->st) != hipSuccess) return 0;
+  if (f[0]) *off = (long long)f[1] - (long long)(ue - kv.first);
+  else if (f[2]) *off = (long long)f[3];
+  const int bad = (f[0] != 0) + (f[2] != 0);
+  if (bad && getenv("TSX_POOL_VERBOSE"))
+    fprintf(stderr, "[tsx_pool] pid %d: red zone of a %zu-byte piece at %p damaged: %llu bytes in front, %llu behind, first at %lld from its end\n",
+            (int)getpid(), kv.second.user, (const void *)u, f[0], f[2], *off);
+  return bad;
 }
 
 // pattern, watch, zero: `p` (bytes) has just come from the driver
@@ -147,7 +206,10 @@ hipError_t new_slab(Pool *P, size_t bytes, char **out) {
   if (e != hipSuccess) return e;
   if ((e = hipMalloc((void **)&base, bytes)) != hipSuccess) return e;
   P->driver_allocs++;
-  if ((e = quarantine(P, base, bytes)) != hipSuccess) return e;
+  if ((e = quarantine(P, base, bytes)) != hipSuccess) {
+    (void)hipFree(base);
+    return e;
+  }
   P->m.add_slab(base, bytes);
   *out = base;
   return hipSuccess;
@@ -162,17 +224,29 @@ hipError_t tsx_dev_malloc_bytes(void **out, size_t bytes) {
   if (getenv("TSX_POOL") && atoi(getenv("TSX_POOL")) == 0) return hipMalloc(out, bytes);  // A/B: straight to the driver
   Pool *P = pool_of(dev);
   std::lock_guard<std::mutex> lk(P->mu);
-  const size_t need = TsxPieceMap::rounded(bytes);
-  if ((*out = P->m.take(need))) return hipSuccess;
-  // a new slab: small requests share slabs of TSX_POOL_SLAB_MB (default 64), a large one gets a slab of its own size
-  const size_t slab_min = (size_t)env_ll("TSX_POOL_SLAB_MB", 64) << 20;
-  const size_t sz = need > slab_min ? need : slab_min;
-  char *base = nullptr;
-  e = new_slab(P, sz, &base);
-  if (e != hipSuccess && sz > need) e = new_slab(P, need, &base);  // (a nearly full device: exactly what was asked for)
-  if (e != hipSuccess) return e;
-  *out = P->m.take(need);
-  return *out ? hipSuccess : hipErrorOutOfMemory;
+  const int poison = poison_byte();
+  const size_t need = poison < 0 ? TsxPieceMap::rounded(bytes) : TsxPieceMap::zoned_bytes(bytes);
+  auto take = [&]() { return poison < 0 ? P->m.take(need) : P->m.take_zoned(bytes); };
+  if (!(*out = take())) {
+    // a new slab: small requests share slabs of TSX_POOL_SLAB_MB (default 64), a large one gets a slab of its own size
+    const size_t slab_min = (size_t)env_ll("TSX_POOL_SLAB_MB", 64) << 20;
+    const size_t sz = need > slab_min ? need : slab_min;
+    char *base = nullptr;
+    e = new_slab(P, sz, &base);
+    if (e != hipSuccess && sz > need) {  // (a nearly full device: exactly what was asked for)
+      e = new_slab(P, need, &base);
+      if (e == hipSuccess) (void)hipGetLastError();  // (the failed slab's out-of-memory must not stay behind as the last error)
+    }
+    if (e != hipSuccess) return e;
+    if (!(*out = take())) return hipErrorOutOfMemory;
+  }
+  if (poison >= 0) {  // red zones around, the poison byte inside -- also in a slab zeroed a moment ago
+    char *piece = (char *)*out - kZone;
+    fill(P, piece, need, zone_byte(poison));
+    fill(P, *out, bytes, (unsigned char)poison);
+    if ((e = hipStreamSynchronize(P->st)) != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t tsx_dev_free(void *p) {
@@ -195,6 +269,23 @@ hipError_t tsx_dev_free(void *p) {
   }
   if (!P) return hipFree(p);  // not ours (TSX_POOL=0 allocations)
   std::lock_guard<std::mutex> lk(P->mu);
+  auto it = P->m.find_user((const char *)p);
+  if (it == P->m.pieces.end() || it->second.free) return hipErrorInvalidValue;
+  if (it->second.zoned) {
+    long long off = 0;
+    const int bad = check_zones(P, *it, &off);
+    if (bad && !P->zones_bad_at_free) {
+      P->first_bad_user = (long long)it->second.user;
+      P->first_bad_off = off;
+    }
+    P->zones_bad_at_free += bad;
+  }
+  const int poison = poison_byte();
+  if (poison >= 0) {  // a read through a stale pointer finds the poison byte
+    fill(P, it->first, it->second.bytes, (unsigned char)poison);
+    const hipError_t e2 = hipStreamSynchronize(P->st);
+    if (e == hipSuccess) e = e2;
+  }
   if (!P->m.give((char *)p)) return hipErrorInvalidValue;
   return e;
 }
@@ -247,5 +338,66 @@ extern "C" int tsx_pool_stats(int device, int64_t *out8) {
   out8[5] = P->wiped_words;
   out8[6] = P->first_wipe_us;
   out8[7] = P->guard_us_spent;
+  return TSX_OK;
+}
+
+// out4 = {live pieces with red zones checked now, damaged zones found now + those found by tsx_dev_free since the last reset, requested
+// bytes of the first damaged piece, offset of its first damaged byte from the end of the requested bytes (negative: the front zone)}
+static void pool_check(Pool *P, int reset, int64_t *out4) {
+  long long n = 0, bad = P->zones_bad_at_free, user = P->first_bad_user, off = P->first_bad_off;
+  for (auto &kv : P->m.pieces) {
+    if (kv.second.free || !kv.second.zoned) continue;
+    ++n;
+    long long o = 0;
+    const int b = check_zones(P, kv, &o);
+    if (b && !bad) {
+      user = (long long)kv.second.user;
+      off = o;
+    }
+    bad += b;
+  }
+  out4[0] = n;
+  out4[1] = bad;
+  out4[2] = bad ? user : 0;
+  out4[3] = bad ? off : 0;
+  if (reset) P->zones_bad_at_free = P->first_bad_user = P->first_bad_off = 0;
+}
+extern "C" int tsx_pool_check(int device, int reset, int64_t *out4) {
+  ARGCHK(out4, "tsx_pool_check: null");
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TSX_ERR_NO_DEVICE;
+  Pool *P = pool_of(device);
+  std::lock_guard<std::mutex> lk(P->mu);
+  HIPCHK(pool_tools(P));
+  pool_check(P, reset, out4);
+  return TSX_OK;
+}
+
+// The detector's self test: takes a zoned piece of `bytes`, writes `nbytes` bytes at `off` from the end of the requested bytes -- only
+// ever inside the piece's own red zones (refused otherwise, and outside TSX_POOL_POISON) --, reports tsx_pool_check (no reset) into
+// out4 while the piece is live, and frees it (tsx_dev_free finds the damage a second time).
+extern "C" int tsx_pool_debug_overrun(int64_t bytes, int64_t off, int64_t nbytes, int64_t *out4) {
+  ARGCHK(out4 && bytes > 0 && nbytes > 0, "tsx_pool_debug_overrun: bad arguments");
+  const int poison = poison_byte();
+  ARGCHK(poison >= 0, "tsx_pool_debug_overrun: TSX_POOL_POISON is not set");
+  const long long behind = (long long)(TsxPieceMap::zoned_bytes((size_t)bytes) - kZone) - bytes;  // zone bytes past the end
+  ARGCHK((off >= 0 && off + nbytes <= behind) || (off < 0 && off >= -(bytes + (long long)kZone) && off + nbytes <= -bytes),
+         "tsx_pool_debug_overrun: the damage must lie inside the piece's red zones");
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  Pool *P = pool_of(dev);
+  {
+    TsxDevTmp piece;  // (freed on every exit path: tsx_dev_free checks its zones once more)
+    HIPCHK(piece.alloc((size_t)bytes));
+    {
+      std::lock_guard<std::mutex> lk(P->mu);
+      auto it = P->m.find_user(piece.as<char>());
+      ARGCHK(it != P->m.pieces.end() && it->second.zoned && it->second.user == (size_t)bytes,
+             "tsx_pool_debug_overrun: the piece has no red zones (TSX_POOL=0?)");
+    }
+    HIPCHK(hipMemsetAsync(piece.as<char>() + bytes + off, poison ^ 0x3c, (size_t)nbytes, P->st));
+    HIPCHK(hipStreamSynchronize(P->st));
+    std::lock_guard<std::mutex> lk(P->mu);
+    pool_check(P, 0, out4);
+  }
   return TSX_OK;
 }

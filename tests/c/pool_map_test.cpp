@@ -1,6 +1,8 @@
 // CPU test of the device memory pool's bookkeeping (tenstream_amd/csrc/tsx_pool_map.hpp): random request / return sequences over a few
 // slabs against the invariants -- every byte of every slab belongs to exactly one piece, live pieces never overlap, a returned piece
-// merges with free neighbours of its own slab only, everything returned = one free piece per slab again, best fit.
+// merges with free neighbours of its own slab only, everything returned = one free piece per slab again, best fit.  Pieces with red
+// zones (TSX_POOL_POISON) are mixed in: user pointer <-> piece round trip, the zones lie inside the piece (so never over another
+// piece's user bytes), a zoned piece is returned through its user pointer only.
 //   g++ -O1 -std=c++17 -I tenstream_amd/csrc -o pool_map_test tests/c/pool_map_test.cpp && ./pool_map_test
 #include <cstdio>
 #include <cstdlib>
@@ -42,33 +44,54 @@ int main() {
   m.add_slab(base, 1 << 20);
   m.add_slab(base + (1 << 20), 1 << 20);            // adjacent to the first
   m.add_slab(base + (8 << 20), 4 << 20);
-  std::vector<std::pair<char *, size_t>> mine;
+  struct Mine {
+    char *first;   // user pointer
+    size_t second; // bytes the user may touch
+    bool zoned;
+  };
+  const size_t Z = TsxPieceMap::kZone;
+  std::vector<Mine> mine;
   for (int step = 0; step < 200000; ++step) {
     const bool want = mine.empty() || (rng() % 100) < 52;
     if (want) {
       const size_t sizes[] = {1, 16, 255, 256, 257, 4096, 65536, 300000, 1 << 20, (1 << 20) + 1, 3 << 20};
-      const size_t need = TsxPieceMap::rounded(sizes[rng() % 11] + (rng() % 3 == 0 ? rng() % 1000 : 0));
+      const size_t req = sizes[rng() % 11] + (rng() % 3 == 0 ? rng() % 1000 : 0);
+      const bool zoned = rng() % 3 == 0;
+      const size_t need = zoned ? TsxPieceMap::zoned_bytes(req) : TsxPieceMap::rounded(req);
       // best fit: no free piece that holds the request may be smaller than the one taken
       size_t best = ~(size_t)0;
       for (auto &kv : m.pieces)
         if (kv.second.free && kv.second.bytes >= need && kv.second.bytes < best) best = kv.second.bytes;
-      char *p = m.take(need);
+      char *p = zoned ? m.take_zoned(req) : m.take(need);
       if ((best == ~(size_t)0) != (p == nullptr)) return fail("take succeeds exactly where a free piece holds the request", step);
       if (p) {
         if (((size_t)(p - base) & (TsxPieceMap::kAlign - 1)) != 0) return fail("alignment", step);
+        // the piece behind the user pointer: its start, its size, its zones
+        auto it = m.find_user(p);
+        if (it == m.pieces.end() || it->second.free || it->second.zoned != zoned || TsxPieceMap::user_of(*it) != p)
+          return fail("user pointer -> piece -> user pointer", step);
+        if (it->second.bytes != need || (zoned && (it->first + Z != p || it->second.user != req ||
+                                                   p + req + Z > it->first + it->second.bytes)))
+          return fail("a zoned piece holds kZone, the request (rounded), kZone", step);
+        if (!m.owns(p) || (zoned && (m.owns(it->first) || m.owns(p + 256))) || m.owns(p + 1))
+          return fail("owns: user pointers only", step);
+        // whole pieces (zones included) never overlap another piece's user bytes
         for (auto &o : mine)
-          if (p < o.first + o.second && o.first < p + need) return fail("two live pieces overlap", step);
-        // the piece came out of the smallest fitting free piece: what is left of it is best - need
-        mine.emplace_back(p, need);
+          if (it->first < o.first + o.second && o.first < it->first + it->second.bytes) return fail("a piece overlaps live user bytes", step);
+        mine.push_back({p, req, zoned});
       }
     } else {
       const size_t q = rng() % mine.size();
       if (!m.give(mine[q].first)) return fail("give refuses a live piece", step);
       if (m.give(mine[q].first)) return fail("give accepts a piece twice", step);
+      if (mine[q].zoned && m.give(mine[q].first - Z)) return fail("give accepts the start of a returned zoned piece", step);
       mine[q] = mine.back();
       mine.pop_back();
     }
     if ((step % 97) == 0 && !consistent(m)) return fail("pieces do not tile the slabs / counters disagree / unmerged free neighbours", step);
+    if ((step % 997) == 0)
+      for (auto &kv : m.pieces)
+        if (kv.second.free && (kv.second.zoned || kv.second.user)) return fail("a free piece keeps red zones", step);
   }
   for (auto &o : mine)
     if (!m.give(o.first)) return fail("final give", -1);

@@ -22,10 +22,20 @@ def _free_port():
 
 
 def _guarded(fn, rank, *args):
-    """run a worker; report its exception text through the shared dict instead of only an exit code"""
+    """run a worker; report its exception text through the shared dict instead of only an exit code.  With the pool's hostile-memory
+    mode inherited (TSX_POOL_POISON, tests/test_gpu_pool_hostile.py) the rank checks its own pool's red zones before it exits."""
     ret = args[-1]
     try:
         fn(rank, *args)
+        if os.environ.get("TSX_POOL_POISON"):
+            import ctypes
+            import gc
+
+            from tenstream_amd import _lib
+
+            gc.collect()
+            st = (ctypes.c_int64 * 4)()
+            assert _lib.load().tsx_pool_check(-1, 0, st) == 0 and st[1] == 0, f"rank {rank}: red zones damaged {list(st)}"
     except Exception:  # noqa: BLE001
         import traceback
 
