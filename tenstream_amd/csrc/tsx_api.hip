@@ -1273,7 +1273,7 @@ static int krylov_run_with_retry(tsx_solver *s, tsx_ksp_opts *o) {
   tsx_ksp_opts o2 = *o;
   o2.fp32_directions = 0;
   o2.pc_coeff_fp16 = 0;
-  o2.pc = TSX_PC_REDBLACK;  // on the exact blocks (tsx_pcx.hip); zebra rows where that is not available (prepare_ksp)
+  o2.pc = TSX_PC_REDBLACK;  // on the exact blocks (tsx_pcx.hip, 3_10 and 8_16); zebra rows on odd grids (prepare_ksp)
   o2.pc_sweeps = 0;         // ... with that path's own pass count
   tsx_ksp_opts o3;
   if ((rc = prepare_ksp(s, &o2, &o3))) return rc;
@@ -1411,7 +1411,9 @@ static int prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o)
     // pass (36 us on 256 x 256 x 64) is cheap next to the operator and the vector updates of an iteration (1.3 ms), and 20
     // passes need 6 iterations where 10 need 10 -- and 10 passes with the one-lane-per-column kernels (zebra rows, odd grids)
     const bool scan = s->pc == TSX_PC_REDBLACK && s->mixed && tsx_pcs_eligible(s);
-    const bool exact_scan = s->pc == TSX_PC_REDBLACK && !s->mixed;  // tsx_pcx.hip: the pass count measured in round 6 (profiles/r06)
+    // tsx_pcx.hip: the pass count measured in round 6 on 3_10 (profiles/r06).  8_16's exact scan, config 5 (256 x 256 x 64, default
+    // tolerances): 14 / 20 / 28 passes take 8 / 5 / 4 iterations, 251 / 232 / 254 ms -- 20 passes there too
+    const bool exact_scan = s->pc == TSX_PC_REDBLACK && !s->mixed;
     // round 3: with the side -> top couplings in fp16 (3_10 scan kernels, tsx_k_pcs_pack_rec1h) the residual after 5 iterations of 20 passes
     // sits at 1.02-1.08e-5 on every measured domain -- 22 passes take it below the reference's rtol 1e-5: 5 iterations instead
     // of 6 (256 x 256 x 64: 18.7 -> 16.4 ms; 128 x 128: 6.05 -> 5.29 ms; all blocks distinct: 35.7 -> 31.5 ms; 24 / 26 passes:

@@ -144,13 +144,15 @@ static int apply_pc(tsx_solver *s, const double *v, ZT *z, bool in_solve) {
       return TSX_OK;
     }
   }
-  if constexpr (std::is_same<ZT, double>::value && NTOP == 2) {
-    if (s->pc == TSX_PC_REDBLACK) return tsx_pcx_apply(s, v, z, done);  // exact blocks, fp64 iterates, scan over the levels (tsx_pcx.hip)
+  if constexpr (std::is_same<ZT, double>::value) {
+    // exact blocks, fp64 iterates, scan over the levels (tsx_pcx.hip; 3_10 and 8_16, dispatched on geo.ntop)
+    if (s->pc == TSX_PC_REDBLACK) return tsx_pcx_apply(s, v, z, done);
   }
   if (s->pc == TSX_PC_ZEBRA) {
     const int P = s->pc_sweeps + 1;
     ZT *alt = (ZT *)s->vw;
-    // lagged x coupling: 3_10 kernels and the packed 8_16 kernel; the generic (exact) 8_16 kernel couples in y only
+    // lagged x coupling: 3_10 kernels and the packed 8_16 kernel; the generic (exact) 8_16 kernel couples in y only (on the exact
+    // blocks 8_16 gets the red-black scan wherever tsx_pcx_eligible holds: these rows run there on odd grids only)
     const bool xl = g.ym >= 2 && (NTOP == 2 || std::is_same<ZT, float>::value);
     auto buf = [&](int pass) {  // buffer a pass writes: its colour's last pass writes z, alternating backwards
       const int last = ((P - 1) % 2 == pass % 2) ? P - 1 : P - 2;
