@@ -50,6 +50,8 @@ def parse(argv=None):
                     "g-points at the same time")
     ap.add_argument("--calls", type=int, default=2, help="radiation calls (time steps); the first one is cold")
     ap.add_argument("--pc-sweeps", type=int, default=0, help="0 = library default")
+    ap.add_argument("--collapse", type=int, default=0, help="also run the loop with init_pprts' collapseindex = N (-1: every background "
+                    "layer, n_bg as atm_ke counts them, src/tenstr_atm.F90:508-512) and report it beside the headline (not part of it)")
     ap.add_argument("--phi0", type=float, default=180.0)
     ap.add_argument("--theta0", type=float, default=40.0)
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (the oracle's restatement of the reference's "
@@ -66,7 +68,7 @@ def column_dz(Nz, n_bg, dz_dyn=50.0):
     return dz
 
 
-def run_loop(args, dev, rank=0, world=1, all_reduce=None):
+def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
     import torch
 
     from tenstream_amd import lut as LUT
@@ -107,7 +109,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
     Tdir, Sdir = LUT.synthetic_direct_tables(dax)
     Ps = []
     for _ in range(K):
-        Pk = PprtsSolver(Nz, Nx, Ny, dx, dx, args.phi0, args.theta0, device=dev.index)
+        Pk = PprtsSolver(Nz, Nx, Ny, dx, dx, args.phi0, args.theta0, device=dev.index, collapseindex=collapse)
         Pk.set_lut_diffuse(LUT.synthetic_diffuse_table("3_10"), LUT.diffuse_axes("3_10"))
         Pk.set_lut_direct(Tdir, Sdir, dax)
         Ps.append(Pk)
@@ -120,9 +122,11 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
     lo, hi = (rank * ng) // world, ((rank + 1) * ng) // world   # contiguous blocks: uid - 1 stays on the same rank
     mine = list(range(lo, hi))
 
-    L = Nz + 1
+    Nzs = Ps[0].Nz   # the solver's layers: Nz, or Nz - collapse + 1
+    dz_s = dz_d if Nzs == Nz else dz_d[:, :, Nz - Nzs:].contiguous()   # layer k's volume is dz(atmk(k)) (src/pprts.F90:5483-5503)
+    L = Nzs + 1
     new_acc = lambda: [torch.zeros((Ny, Nx, L), dtype=torch.float64, device=dev), torch.zeros((Ny, Nx, L), dtype=torch.float64, device=dev),
-                       torch.zeros((Ny, Nx, Nz), dtype=torch.float64, device=dev), torch.zeros((Ny, Nx, L), dtype=torch.float64, device=dev)]
+                       torch.zeros((Ny, Nx, Nzs), dtype=torch.float64, device=dev), torch.zeros((Ny, Nx, L), dtype=torch.float64, device=dev)]
     acc = new_acc()
     accs = [acc] + [new_acc() for _ in range(K - 1)]          # one accumulator and one scratch set per instance
     tmps = [[torch.empty_like(a) for a in acc] for _ in range(K)]
@@ -147,7 +151,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
         # Left on the device (four sums in one small tensor): the host reads all of them after the loop, not per g-point
         edn, eup, abso, edir = tmp
         bal = torch.stack(((edn[:, :, 0] + edir[:, :, 0] - eup[:, :, 0]).sum(), (edn[:, :, -1] + edir[:, :, -1] - eup[:, :, -1]).sum(),
-                           (abso * dz_d).sum(), eup[:, :, -1].sum()))
+                           (abso * dz_s).sum(), eup[:, :, -1].sum()))
         return info, bal
 
     def sync():
@@ -222,7 +226,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
             P0.get_result(out=tmp0)
             for a, t in zip(acc0, tmp0):
                 a += t
-            (tmp0[2] * dz_d).sum()
+            (tmp0[2] * dz_s).sum()
             sync()
             t3 = time.perf_counter()
             ph["set_optical_properties"] += t1 - t0
@@ -265,7 +269,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
         except Exception as e:   # noqa: BLE001
             roofline = {"error": str(e)}
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and args.sw > 0:
+    if rank == 0 and not args.no_cpu_baseline and args.sw > 0 and collapse == 1:
         # CPU baseline, one g-point (the solar one with the median optical-depth factor): the very diffuse system the device
         # solved -- its blocks, 1-D layers, Eddington coefficients and right-hand side read back -- through the oracle's
         # restatement of the reference's default CPU path (assembled AIJ + FBCGS + PCBJACOBI / ILU(0), one subdomain per usable
@@ -299,7 +303,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None):
                "loop_extrapolated_with_assembly_s": ng * (oi["t_solve"] + oi["t_assemble"] + oi["t_factor"])}
     for Pk in Ps:
         Pk.close()
-    return dict(ng=ng, rank_gpoints=len(mine), n1d_layers=n1d, calls=calls, mu0=mu0, cpu_baseline=cpu, breakdown=breakdown, roofline=roofline)
+    return dict(ng=ng, rank_gpoints=len(mine), n1d_layers=n1d, solver_layers=Nzs, calls=calls, mu0=mu0, cpu_baseline=cpu, breakdown=breakdown, roofline=roofline)
 
 
 def main():
@@ -316,11 +320,25 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)
     R = run_loop(args, dev, rank, world, all_reduce=(dist.all_reduce if world > 1 else None))
-    secs = [c["seconds"] for c in R["calls"]]
-    if world > 1:
-        tt = torch.tensor(secs, dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        secs = [float(v) for v in tt.tolist()]
+
+    def seconds(R):
+        secs = [c["seconds"] for c in R["calls"]]
+        if world > 1:
+            tt = torch.tensor(secs, dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            secs = [float(v) for v in tt.tolist()]
+        return secs
+
+    secs = seconds(R)
+    extra = {}
+    if args.collapse:   # a leg of its own, reported beside the headline: the same loop with the background collapsed into one layer
+        c = min(args.nz_background, args.nz - 1) if args.collapse < 0 else args.collapse
+        Rc = run_loop(args, dev, rank, world, all_reduce=(dist.all_reduce if world > 1 else None), collapse=c)
+        sc = seconds(Rc)
+        extra = {"collapse": {"collapseindex": c, "solver_layers": Rc["solver_layers"], "value": R["ng"] / sc[-1], "unit": "g-points/s",
+                              "seconds": sc[-1], "calls": [dict(cc, seconds=s_, gpoints_per_s=R["ng"] / s_) for cc, s_ in zip(Rc["calls"], sc)],
+                              "breakdown": Rc["breakdown"], "note": "reported only: init_pprts' collapseindex merges the top layers into "
+                                                                    "one (tsx_pprts_set_collapse); the headline is the uncollapsed loop"}}
     if rank == 0:
         Nx, Ny, Nz, ng = args.nx, args.ny, args.nz, R["ng"]
         last = len(secs) - 1
@@ -335,7 +353,7 @@ def main():
                        "calls": [dict(c, seconds=s_, gpoints_per_s=ng / s_) for c, s_ in zip(R["calls"], secs)],
                        "breakdown": R["breakdown"]},
             "roofline": R["roofline"],
-            "cpu_baseline": R["cpu_baseline"]}))
+            "cpu_baseline": R["cpu_baseline"], **extra}))
     if world > 1:
         dist.destroy_process_group()
 

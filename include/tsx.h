@@ -308,6 +308,22 @@ int tsx_lut_load_direct_mmap4(tsx_solver *s, const char *tdir_path, const char *
 int tsx_pprts_set_optical_properties(tsx_solver *s, const double *albedo, const double *kabs, const double *ksca,
                                      const double *g, const double *dz, const double *planck, const double *planck_srfc,
                                      double dx, double dy, int ldelta_scaling, int where);
+/* init_pprts(..., collapseindex) (src/pprts.F90:213, 229, 849-853, 1067-1078): collapse the top c = collapseindex atmosphere
+ * layers into solver layer 0.  Call after tsx_create and tsx_pprts_set_angles; tsx_grid.Nz stays the solver's layer count Nz.
+ * With c > 1 tsx_pprts_set_optical_properties takes kabs / ksca / g / dz of Nz + c - 1 atmosphere layers and planck of Nz + c
+ * levels; solver layer k is atmosphere layer atmk(k) = k + c - 1 (src/pprts_base.F90:1092).  c <= 1 switches collapse off.  On
+ * the device: delta scaling, 1-D detection (:669-677) and the Eddington coefficients (:1962-1992) on the atmosphere's layers, the
+ * top c layers forced 1-D (:693-705; the reference only warns when one was not), the prefix count (:708-719) and
+ * unconstrained_fraction (:721-723) over the atmosphere's layers; then `adding` (:2080-2198) merges layers 0..c-1 per column into
+ * solver layer 0 (a11 = Tbot, a12 = Rtop, a13 = rdir, a23 = sdir, a33 = tdir) and, with planck, atm%Btop = Eup(1) / pi and
+ * atm%Bbot = Edn(c+1) / pi of schwarzschild over those layers (:2192-2196, src/schwarzschild.F90:69-135), which the thermal
+ * source of layer 0 emits instead of B_eff * emissivity (:4875-4877).  The direct beam and the absorption read the merged layer
+ * and the fields at atmk(k) (:4511, 4618, 4707-4721, 5307, 5361, 5483-5503: the volume of layer 0 is Az * dz(atmk(0))).
+ * Results come out on the solver's grid (Nz + 1 levels, Nz layers, :229).  A changed c is a new atmosphere: the coefficients,
+ * stored solutions and the initial guess are dropped.  With collapse on, tsx_pprts_set_optprop, tsx_diff_set_coeffs,
+ * tsx_diff_set_optprop, tsx_dir_set_coeffs and tsx_setup_b_solar / _thermal return TSX_ERR_UNSUPPORTED: coefficients derived
+ * by the caller cannot carry atm%Btop / atm%Bbot. */
+int tsx_pprts_set_collapse(tsx_solver *s, int32_t collapseindex);
 /* optical properties of one g-point, (zs:ze-1, xs:xe, ys:ye) real64, already delta-scaled; a11..a33 only read for
  * 1-D layers (eddington coefficients, src/pprts.F90:1962-1992); planck (zs:ze, xs:xe, ys:ye) or NULL for solar;
  * planck_srfc (xs:xe, ys:ye) or NULL as above */
@@ -333,7 +349,9 @@ int tsx_pprts_get_result(tsx_solver *s, double *edn, double *eup, double *abso, 
  * 3 dir2dir (S*S, zs:ze-1, ...); 4 dir2diff (S*D, ...) -- reference layouts, real64;
  * what tsx_pprts_set_optical_properties derived on the device, (zs:ze-1, xs:xe, ys:ye): 5 kabs, 6 ksca, 7 g after delta scaling
  * (src/pprts.F90:1903-1917); 8..12 the Eddington coefficients a11, a12, a13, a23, a33 of the 1-D layers (:1962-1992; NaN in
- * layers that are not 1-D) */
+ * layers that are not 1-D).  With collapse (tsx_pprts_set_collapse) 5..12 are solver layers, the atmosphere's at atmk(k), and
+ * layer 0 of 8..12 holds the merged coefficients of `adding` (:2174-2186); 13 atm%Btop, 14 atm%Bbot (xs:xe, ys:ye) (:2192-2196),
+ * NaN without planck or without collapse */
 int tsx_pprts_get_field(tsx_solver *s, int which, double *out, int where);
 
 /* ---- coefficient probe: pprts_f2c_opp_get_coeff / _get_info (c_wrapper/f2c_pprts.h:54-83, f2c_pprts.F90:627-760).

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -180,7 +181,7 @@ extern "C" int tsx_determine_ksp_tolerances(const tsx_solver *s, double unconstr
   *maxit = 1000;
   *rtol = 1e-5;
   if (unconstrained_fraction < 0.0)  // the solver's own count of 1-D layers (after tsx_pprts_set_optical_properties)
-    unconstrained_fraction = s->geo.Nz > 0 ? 1.0 - (double)s->n1d / (double)s->geo.Nz : 1.0;
+    unconstrained_fraction = s->geo.Nz > 0 ? tsx_unconstrained_fraction(s) : 1.0;
   double a = 1e-4 * (double)s->grid.glob_xm * (double)s->grid.glob_ym * (double)(s->grid.Nz + 1) * unconstrained_fraction;
   *atol = a > 1e-8 ? a : 1e-8;
   return TSX_OK;
@@ -297,7 +298,7 @@ extern "C" int tsx_destroy(tsx_solver *s) {
                   s->vv,    s->vs,    s->vt,    s->stage_a, s->stage_b, s->sendW, s->sendE, s->sendS, s->sendN, s->recvW,
                   s->recvE, s->recvS, s->recvN, s->partials, s->scal, s->vw, s->pc_tmp, s->lut_diff.d_axes, s->lut_diff.d_table,
                   s->lut_T.d_axes, s->lut_T.d_table, s->lut_S.d_axes, s->lut_S.d_table, s->dirT, s->dirS, s->d_kabs, s->d_ksca,
-                  s->d_g, s->d_dz, s->a13, s->a23, s->a33, s->planck, s->bsrfc, s->edir_a, s->edir_b, s->dsc, s->abso, s->cell_samp, s->dd_colsum, s->pcx_rec, s->pcx_vz, s->flow_state, s->flow_prog, s->flow_zb8, s->flow_pr_dev};
+                  s->d_g, s->d_dz, s->a13, s->a23, s->a33, s->planck, s->bsrfc, s->edir_a, s->edir_b, s->dsc, s->abso, s->cell_samp, s->dd_colsum, s->pcx_rec, s->pcx_vz, s->flow_state, s->flow_prog, s->flow_zb8, s->flow_pr_dev, s->ca_buf, s->ca_B};
   for (void *p : ptrs)
     if (p) (void)tsx_dev_free(p);
   if (s->vph && s->vph != s->vp) (void)tsx_dev_free(s->vph);
@@ -565,6 +566,7 @@ extern "C" int tsx_diff_set_coeffs(tsx_solver *s, const void *diff2diff, int coe
                                    const double *a11, const double *a12, const double *albedo, int where) {
   ARGCHK(s && diff2diff && l1d && albedo, "tsx_diff_set_coeffs: null argument");
   ARGCHK(coeff_kind == 4 || coeff_kind == 8, "tsx_diff_set_coeffs: coeff_kind must be 4 or 8");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_diff_set_coeffs")) return rc_c;
   HIPCHK(hipSetDevice(s->device));
   const TsxGeo &g = s->geo;
   const int DD = g.D * g.D;
@@ -783,6 +785,7 @@ extern "C" int tsx_diff_set_optprop(tsx_solver *s, const double *kabs, const dou
                                     const double *albedo, int where) {
   ARGCHK(s && kabs && ksca && g && dz && l1d && albedo, "tsx_diff_set_optprop: null argument");
   ARGCHK(dx > 0, "tsx_diff_set_optprop: dx <= 0");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_diff_set_optprop")) return rc_c;
   if (!s->lut_diff.ready) {
     tsx_set_error("tsx_diff_set_optprop: load the diffuse LUT first (tsx_lut_set_diffuse / tsx_lut_load_diffuse_mmap4)");
     return TSX_ERR_STATE;

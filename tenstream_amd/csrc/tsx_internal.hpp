@@ -188,7 +188,8 @@ struct tsx_solver {
   bool x_is_zero = false;      // the initial guess in vx is known to be zero on every rank (krylov_begin then skips A x0)
   bool dd_hash_ready = false;  // the hashes of the current blocks already sit in dd_scratch (left by tsx_k_lut_diff2diff)
   size_t dd_scratch_bytes;
-  int n1d;             // number of 1-D layers (unconstrained_fraction = 1 - n1d/Nz, src/pprts.F90:721-723)
+  int n1d;             // number of 1-D layers (unconstrained_fraction = 1 - n1d/Nz, src/pprts.F90:721-723; with collapse: of the
+                       // atmosphere's Nz + collapse - 1 layers, tsx_unconstrained_fraction)
   TsxLutHost lut_diff;
 
   // Krylov work vectors (internal layout, N doubles each)
@@ -270,8 +271,21 @@ struct tsx_solver {
   double *pcx_rec = nullptr;  // [7][Nc] fp64 column recurrences of the exact scan preconditioner (tsx_pcx.hip), natural cell order
   bool pcx_valid = false;     // ... belong to the current coefficient set
   double *pcx_vz = nullptr;   // [2][N]: colour-split copies of the right-hand side and the iterate of that path
+  // atmosphere collapse (init_pprts' collapseindex, src/pprts.F90:213, 229, 693-705, 2080-2198; tsx_pprts_set_collapse): the caller's
+  // fields have Nz + collapse - 1 layers, solver layer k is atmosphere layer k + collapse - 1, layer 0 holds the merged top layers
+  int collapse = 1;           // <= 1: off
+  double *ca_buf = nullptr;   // the atmosphere-shaped scratch of tsx_pprts_set_optical_properties (grow-only), see collapse_scratch
+  int ca_nz_cap = 0;          // ... sized for this many atmosphere layers
+  double *ca_B = nullptr;     // [2][ncol]: atm%Btop, atm%Bbot (:2192-2196); NaN without planck
+  bool ca_have_B = false;
   TsxLog *log = nullptr;     // the reference's log events for this path + roctx ranges (tsx_log_enable; off: null)
 };
+
+// atm%unconstrained_fraction (src/pprts.F90:721-723): the share of the ATMOSPHERE's layers that are not 1-D
+static inline double tsx_unconstrained_fraction(const tsx_solver *s) {
+  const int nz = s->collapse > 1 ? s->geo.Nz + s->collapse - 1 : s->geo.Nz;
+  return 1.0 - (double)s->n1d / (double)nz;
+}
 
 // The reference brackets the phases of a solve with PETSc log events (solver%logs, src/pprts_base.F90:176-209; begun / ended at
 // src/pprts.F90:1785-2077 set_optprop, :2694-2756 compute_Edir, :2760-2818 compute_Ediff, :2952-2954 setup_Mdiff, :3012-3021
@@ -303,3 +317,12 @@ struct TsxLogScope {  // begin at construction, end on every exit path
 };
 
 void tsx_set_error(const std::string &msg);
+
+// entries that take coefficients the caller has already derived cannot carry the merged layer of a collapsed atmosphere (nor
+// atm%Btop / atm%Bbot): refused on a handle with tsx_pprts_set_collapse > 1
+static inline int tsx_refuse_collapsed(const tsx_solver *s, const char *who) {
+  if (!s || s->collapse <= 1) return TSX_OK;
+  tsx_set_error(std::string(who) + ": not available with a collapsed atmosphere (tsx_pprts_set_collapse > 1); use "
+                "tsx_pprts_set_optical_properties");
+  return TSX_ERR_UNSUPPORTED;
+}

@@ -611,8 +611,11 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_setup_b_thermal(TsxGeo g, con
                                                                    const double *__restrict__ kabs,
                                                                    const double *__restrict__ dz, double dx, double dy,
                                                                    double *__restrict__ b, const double *__restrict__ colsum,
-                                                                   const int *__restrict__ cidx, long long nent) {
+                                                                   const int *__restrict__ cidx, long long nent,
+                                                                   const double *__restrict__ cB) {
   // colsum (nullable): sum over dst of c(src, :) per distinct block [D][nent] behind the per-cell index cidx (tsx_k_dd_colsum)
+  // cB (nullable): collapsed atmosphere, atm%Btop [ncol] then atm%Bbot [ncol] (tsx_k_collapse_adding): layer 0 emits them
+  // instead of B_eff * emis (lcollapse .and. k == i0, src/pprts.F90:4875-4877)
   constexpr int D = NTOP + 2 * NSIDE;
   const int xm = g.xm, ym = g.ym, Nz = g.Nz, ncol = g.ncol, L = Nz + 1;
   const long long Nc = g.Nc;
@@ -634,10 +637,15 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_setup_b_thermal(TsxGeo g, con
     const double btop = tsx_B_eff(b1, b0, tauz), bbot = tsx_B_eff(b0, b1, tauz);
     if (l1d[k]) {
       const double bfac = pi * Az / tstreams;
-      double emis = 1.0 - a11[c] - a12[c];
-      emis = fmax(0.0, fmin(1.0, emis));
+      if (cB && k == 0) {
 #pragma unroll
-      for (int q = 0; q < NTOP; ++q) b[(size_t)q * Nc + c] = (tsx_inward(q) ? bbot : btop) * bfac * emis;
+        for (int q = 0; q < NTOP; ++q) b[(size_t)q * Nc + c] = (tsx_inward(q) ? cB[ncol + col] : cB[col]) * bfac;
+      } else {
+        double emis = 1.0 - a11[c] - a12[c];
+        emis = fmax(0.0, fmin(1.0, emis));
+#pragma unroll
+        for (int q = 0; q < NTOP; ++q) b[(size_t)q * Nc + c] = (tsx_inward(q) ? bbot : btop) * bfac * emis;
+      }
 #pragma unroll
       for (int d = NTOP; d < D; ++d) b[(size_t)d * Nc + c] = 0.0;
     } else {
@@ -954,5 +962,111 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_eddington(TsxGeo g, const dou
     a13[c] = rdir;
     a23[c] = sdir;
     a33[c] = tdir;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Atmosphere collapse (init_pprts' collapseindex c > 1, src/pprts.F90:213, 229, 693-705, 1067-1078, 2074-2198): the caller's
+// Nz_atm = Nz + c - 1 layers are set up on their own grid (delta scaling, 1-D detection, Eddington coefficients), then the top c of
+// them are merged into solver layer 0 by `adding`, and solver layer k >= 1 is atmosphere layer atmk(k) = k + c - 1
+// (src/pprts_base.F90:1092).
+
+// schwarzschild_radiance (src/schwarzschild.F90:69-80)
+__device__ __forceinline__ double tsx_schwarzschild_radiance(double tau, double B_near, double B_far, double L) {
+  if (tau > 1e-3) {
+    const double tm1 = expm1(-tau);
+    return L * (tm1 + 1) + (B_far - B_near) - (B_near - (B_far - B_near) / tau) * tm1;
+  }
+  return (B_near + B_far) * .5 * tau + L * (1.0 - tau);
+}
+
+// adding (src/pprts.F90:2125-2198) over atmosphere layers 0 .. c-1 of one column per lane; handle_atm_collapse (:2080-2123) calls it
+// with a21 = a12, a22 = a11 (:2072-2073).  In: the atmosphere's cell-indexed Eddington planes a*a[k * ncol + col] (as tsx_k_eddington
+// writes them: a wave reads consecutive columns of one layer), kabs / dz (delta-scaled) and planck (nullable) in the reference layout
+// of the atmosphere.  Out: the merged coefficients at solver layer 0 (a11 = Tbot, a12 = Rtop, a13 = rdir, a23 = sdir, a33 = tdir;
+// a21 = Rbot and a22 = Ttop are never read, :5721, 5729), and with planck Btop = Eup(1) / pi, Bbot = Edn(c+1) / pi of
+// schwarzschild(2, dz * kabs, albedo 0, planck(0..c), opt_srfc_emission = 0) (src/schwarzschild.F90:82-135) in B[col], B[ncol + col].
+// The layers are walked twice from memory (top-down, bottom-up): no per-lane arrays, so nothing spills to scratch.
+__global__ __launch_bounds__(TSX_BLOCK) void tsx_k_collapse_adding(int ncol, int c, int nz_atm, const double *__restrict__ a11a,
+                                                                   const double *__restrict__ a12a, const double *__restrict__ a13a,
+                                                                   const double *__restrict__ a23a, const double *__restrict__ a33a,
+                                                                   const double *__restrict__ kabs, const double *__restrict__ dz,
+                                                                   const double *__restrict__ planck, double *__restrict__ a11,
+                                                                   double *__restrict__ a12, double *__restrict__ a13,
+                                                                   double *__restrict__ a23, double *__restrict__ a33,
+                                                                   double *__restrict__ B) {
+  const int col = blockIdx.x * TSX_BLOCK + threadIdx.x;
+  if (col >= ncol) return;
+  double t = a11a[col], r = a12a[col], tdir = a33a[col], rdir = a13a[col], sdir = a23a[col];
+  for (int k = 1; k < c; ++k) {  // reflectivity as seen from top
+    const size_t q = (size_t)k * ncol + col;
+    const double b11 = a11a[q], b12 = a12a[q], b13 = a13a[q], b23 = a23a[q], b33 = a33a[q];
+    const double rl = r, tl = t;
+    r = r + (b12 * (t * t)) / (1.0 - r * b12);
+    t = t * b11 / (1.0 - rl * b12);
+    sdir = (b11 * sdir + tdir * b13 * rl * b11) / (1.0 - rl * b12) + tdir * b23;
+    rdir = rdir + (tdir * b13 + sdir * b12) * tl;
+    tdir = tdir * b33;
+  }
+  const double Rtop = r;  // (Ttop = t would go to a22, which nothing reads)
+  t = a11a[(size_t)(c - 1) * ncol + col];  // a22(N)
+  r = a12a[(size_t)(c - 1) * ncol + col];  // a21(N)
+  for (int k = c - 2; k >= 0; --k) {  // reflectivity as seen from bottom
+    const size_t q = (size_t)k * ncol + col;
+    const double b11 = a11a[q], b12 = a12a[q];
+    const double rl = r;
+    r = b12 + (r * (b11 * b11)) / (1.0 - r * b12);
+    t = t * b11 / (1.0 - rl * b12);  // a21(k) = a12(k)
+  }
+  a11[col] = t;     // Tbot
+  a12[col] = Rtop;
+  a13[col] = rdir;
+  a23[col] = sdir;
+  a33[col] = tdir;
+  if (!planck) return;
+  const double pi = 3.14159265358979323846;
+  const double pt[2] = {0.5 - 0.5 / 1.7320508075688772, 0.5 + 0.5 / 1.7320508075688772};
+  const size_t r0 = (size_t)nz_atm * col, l0 = (size_t)(nz_atm + 1) * col;
+  double edn = 0.0, eup = 0.0;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {  // zero incoming radiation at TOA
+    const double mu = pt[m];
+    double L = 0.0;
+    for (int k = 0; k < c; ++k) L = tsx_schwarzschild_radiance(dz[r0 + k] * kabs[r0 + k] / mu, planck[l0 + k], planck[l0 + k + 1], L);
+    edn += L * mu * 0.5;
+  }
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {  // surface: Bsrfc = opt_srfc_emission = 0, albedo 0
+    const double mu = pt[m];
+    double L = 0.0;
+    for (int k = c - 1; k >= 0; --k) L = tsx_schwarzschild_radiance(dz[r0 + k] * kabs[r0 + k] / mu, planck[l0 + k + 1], planck[l0 + k], L);
+    eup += L * mu * 0.5;
+  }
+  B[col] = eup * 2 * pi / pi;         // Btop
+  B[ncol + col] = edn * 2 * pi / pi;  // Bbot
+}
+
+// the per-layer fields the rest of the pipeline reads, at atmk(k): kabs, ksca, g, dz (Nz layers) and planck (Nz + 1 levels, nullable),
+// reference layout (k fastest) on both sides
+__global__ __launch_bounds__(TSX_BLOCK) void tsx_k_collapse_views(int ncol, int Nz, int c, const double *__restrict__ kabs_a,
+                                                                  const double *__restrict__ ksca_a, const double *__restrict__ g_a,
+                                                                  const double *__restrict__ dz_a, const double *__restrict__ planck_a,
+                                                                  double *__restrict__ kabs, double *__restrict__ ksca,
+                                                                  double *__restrict__ g, double *__restrict__ dz,
+                                                                  double *__restrict__ planck) {
+  const int nz_atm = Nz + c - 1;
+  const long long nl = (long long)Nz * ncol, np = planck_a ? (long long)(Nz + 1) * ncol : 0;
+  for (long long q = (long long)blockIdx.x * TSX_BLOCK + threadIdx.x; q < nl + np; q += (long long)gridDim.x * TSX_BLOCK) {
+    if (q < nl) {
+      const long long col = q / Nz;
+      const size_t src = (size_t)(q - col * Nz + c - 1) + (size_t)nz_atm * col;
+      kabs[q] = kabs_a[src];
+      ksca[q] = ksca_a[src];
+      g[q] = g_a[src];
+      dz[q] = dz_a[src];
+    } else {
+      const long long u = q - nl, col = u / (Nz + 1);
+      planck[u] = planck_a[(size_t)(u - col * (Nz + 1) + c - 1) + (size_t)(nz_atm + 1) * col];
+    }
   }
 }

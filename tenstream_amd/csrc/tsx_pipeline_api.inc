@@ -411,6 +411,7 @@ extern "C" int tsx_pprts_set_optprop(tsx_solver *s, const double *kabs, const do
                                      const double *a33, const double *planck, const double *planck_srfc, int where) {
   ARGCHK(s && kabs && ksca && g && dz && albedo && l1d, "tsx_pprts_set_optprop: null argument");
   ARGCHK(dx > 0 && dy > 0, "tsx_pprts_set_optprop: dx, dy must be positive");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_pprts_set_optprop")) return rc_c;
   int rc = pipeline_guard(s, "tsx_pprts_set_optprop");
   if (rc) return rc;
   HIPCHK(hipSetDevice(s->device));
@@ -444,6 +445,129 @@ extern "C" int tsx_pprts_set_optprop(tsx_solver *s, const double *kabs, const do
   return TSX_OK;
 }
 
+// 1-D layers of a column of nz layers from the per-layer flags of tsx_k_flag_1d: the bottom layer on its own; the lowest other layer
+// that exceeds drags every layer above it along (src/pprts.F90:670-677); with collapse the top `collapse` layers are 1-D whatever the
+// flags say (:693-705: the reference only warns); then the count of 1-D layers is applied from the top, as the maximum over the ranks
+// (:708-719).  Returns the count (unconstrained_fraction, :721-723).
+static int l1d_from_flags(tsx_solver *s, const std::vector<int> &flags, int collapse, std::vector<uint8_t> &l1d, int *n1d) {
+  const int nz = (int)flags.size();
+  l1d.assign(nz, 0);
+  l1d[nz - 1] = flags[nz - 1] != 0;
+  for (int k = nz - 2; k >= 0; --k)
+    if (flags[k]) {
+      for (int q = 0; q <= k; ++q) l1d[q] = 1;
+      break;
+    }
+  for (int k = 0; k < collapse && k < nz; ++k) l1d[k] = 1;
+  int n = 0;
+  for (int k = 0; k < nz; ++k) n += l1d[k];
+  for (int k = 0; k < n; ++k) l1d[k] = 1;
+  if (s->grid.nranks > 1) {  // the local sets are prefixes, so OR them
+    for (int k0 = 0; k0 < nz; k0 += TSX_NSLOTS) {
+      double v[TSX_NSLOTS] = {0};
+      const int m = nz - k0 < TSX_NSLOTS ? nz - k0 : TSX_NSLOTS;
+      for (int q = 0; q < m; ++q) v[q] = l1d[k0 + q];
+      int rc = allreduce_host(s, v, m);
+      if (rc) return rc;
+      for (int q = 0; q < m; ++q) l1d[k0 + q] = v[q] > 0.0;
+    }
+  }
+  n = 0;
+  for (int k = 0; k < nz; ++k) n += l1d[k];
+  *n1d = n;
+  return TSX_OK;
+}
+
+// The atmosphere-shaped scratch of a collapsed set (pool, allocated on first use, grow-only), for nz_atm layers of ncol columns:
+// kabs, ksca, g, dz [nz_atm * ncol] (reference layout), planck [(nz_atm + 1) * ncol], a11, a12, a13, a23, a33 [nz_atm * ncol] (cell
+// order), l1d [nz_atm] bytes
+struct TsxCollapseScratch {
+  double *kabs, *ksca, *g, *dz, *planck, *a[5];
+  uint8_t *l1d;
+};
+static int collapse_scratch(tsx_solver *s, int nz_atm, TsxCollapseScratch *cs) {
+  const size_t ncol = (size_t)s->geo.ncol, nc = (size_t)nz_atm * ncol;
+  if (nz_atm > s->ca_nz_cap) {
+    if (s->ca_buf) HIPCHK(tsx_dev_free(s->ca_buf));
+    s->ca_buf = nullptr;
+    s->ca_nz_cap = 0;
+    HIPCHK(tsx_dev_malloc((void **)&s->ca_buf, sizeof(double) * (9 * nc + (nz_atm + 1) * ncol + ((size_t)nz_atm + 7) / 8)));
+    s->ca_nz_cap = nz_atm;
+  }
+  if (!s->ca_B) HIPCHK(tsx_dev_malloc((void **)&s->ca_B, sizeof(double) * 2 * ncol));
+  double *p = s->ca_buf;
+  cs->kabs = p, p += nc;
+  cs->ksca = p, p += nc;
+  cs->g = p, p += nc;
+  cs->dz = p, p += nc;
+  cs->planck = p, p += (nz_atm + 1) * ncol;
+  for (int q = 0; q < 5; ++q) cs->a[q] = p, p += nc;
+  cs->l1d = (uint8_t *)p;
+  return TSX_OK;
+}
+
+// tsx_pprts_set_optical_properties with collapse (src/pprts.F90:1764-2077 with atm%lcollapse): delta scaling, 1-D detection and the
+// Eddington coefficients on the atmosphere's Nz + c - 1 layers, handle_atm_collapse (:2080-2123) by tsx_k_collapse_adding, then the
+// solver's fields as the atmosphere's at atmk(k) = k + c - 1.  Leaves what the uncollapsed branch leaves: d_kabs .. d_dz, l1d,
+// a11 .. a33, planck (when given), n1d / any_l1d, the albedo; and atm%Btop / Bbot in ca_B.
+static int collapse_optprop(tsx_solver *s, const double *albedo, const double *kabs, const double *ksca, const double *g,
+                            const double *dz, const double *planck, double dx, int ldelta_scaling, int where) {
+  const TsxGeo &gm = s->geo;
+  const int c = s->collapse, nz_atm = gm.Nz + c - 1;
+  const size_t ncol = (size_t)gm.ncol, nca = (size_t)nz_atm * ncol;
+  const hipMemcpyKind mk = where == TSX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  int rc;
+  TsxCollapseScratch A;
+  if ((rc = collapse_scratch(s, nz_atm, &A))) return rc;
+  if ((rc = keep_field(s, &A.kabs, kabs, nca, where))) return rc;
+  if ((rc = keep_field(s, &A.ksca, ksca, nca, where))) return rc;
+  if ((rc = keep_field(s, &A.g, g, nca, where))) return rc;
+  if ((rc = keep_field(s, &A.dz, dz, nca, where))) return rc;
+  if (planck && (rc = keep_field(s, &A.planck, planck, (size_t)(nz_atm + 1) * ncol, where))) return rc;
+  HIPCHK(hipMemcpyAsync(s->albedo, albedo, sizeof(double) * ncol, mk, s->stream));
+  s->have_albedo = true;
+  if (ldelta_scaling)
+    hipLaunchKernelGGL(tsx_k_delta_scale, dim3(grid_for((long long)nca)), dim3(TSX_BLOCK), 0, s->stream, (long long)nca, A.kabs, A.ksca, A.g);
+  std::vector<int> flags(nz_atm, 0);
+  int *dflags = (int *)s->partials;  // scratch
+  HIPCHK(hipMemsetAsync(dflags, 0, sizeof(int) * nz_atm, s->stream));
+  hipLaunchKernelGGL(tsx_k_flag_1d, dim3(grid_for((long long)nca)), dim3(TSX_BLOCK), 0, s->stream, (long long)nca, nz_atm, A.dz, dx, 2.0, dflags);
+  HIPCHK(hipMemcpyAsync(flags.data(), dflags, sizeof(int) * nz_atm, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  std::vector<uint8_t> l1d;
+  if ((rc = l1d_from_flags(s, flags, c, l1d, &s->n1d))) return rc;
+  s->any_l1d = true;  // layer 0 at least
+  HIPCHK(hipMemcpyAsync(A.l1d, l1d.data(), nz_atm, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipMemcpyAsync(s->l1d, l1d.data() + (c - 1), gm.Nz, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));  // l1d (host vector) must outlive the copies
+  TsxGeo ga = gm;
+  ga.Nz = nz_atm;
+  ga.Nc = (long long)nca;
+  hipLaunchKernelGGL(tsx_k_eddington, dim3(grid_for(ga.Nc)), dim3(TSX_BLOCK), 0, s->stream, ga, A.kabs, A.ksca, A.g, A.dz,
+                     s->sun_costheta, A.l1d, A.a[0], A.a[1], A.a[2], A.a[3], A.a[4]);
+  double **fields[5] = {&s->a11, &s->a12, &s->a13, &s->a23, &s->a33};
+  for (double **f : fields)
+    if (!*f) HIPCHK(tsx_dev_malloc((void **)f, sizeof(double) * gm.Nc));
+  double **views[4] = {&s->d_kabs, &s->d_ksca, &s->d_g, &s->d_dz};
+  for (double **f : views)
+    if (!*f) HIPCHK(tsx_dev_malloc((void **)f, sizeof(double) * gm.Nc));
+  if (planck && !s->planck) HIPCHK(tsx_dev_malloc((void **)&s->planck, sizeof(double) * (gm.Nz + 1) * ncol));
+  if (!planck) HIPCHK(hipMemsetAsync(s->ca_B, 0xff, sizeof(double) * 2 * ncol, s->stream));  // NaN: no thermal terms
+  hipLaunchKernelGGL(tsx_k_collapse_adding, dim3((unsigned)((ncol + TSX_BLOCK - 1) / TSX_BLOCK)), dim3(TSX_BLOCK), 0, s->stream,
+                     (int)ncol, c, nz_atm, A.a[0], A.a[1], A.a[2], A.a[3], A.a[4], A.kabs, A.dz, planck ? A.planck : (const double *)nullptr,
+                     s->a11, s->a12, s->a13, s->a23, s->a33, s->ca_B);
+  // solver layers k >= 1: atmosphere layers k + c - 1 of the cell-indexed planes
+  if (gm.Nz > 1)
+    for (int q = 0; q < 5; ++q)
+      if ((rc = tsx_d2d(s, *fields[q] + ncol, A.a[q] + (size_t)c * ncol, sizeof(double) * (gm.Nz - 1) * ncol))) return rc;
+  const long long nv = (long long)gm.Nz * ncol + (planck ? (long long)(gm.Nz + 1) * ncol : 0);
+  hipLaunchKernelGGL(tsx_k_collapse_views, dim3(grid_for(nv)), dim3(TSX_BLOCK), 0, s->stream, (int)ncol, gm.Nz, c, A.kabs, A.ksca, A.g,
+                     A.dz, planck ? A.planck : (const double *)nullptr, s->d_kabs, s->d_ksca, s->d_g, s->d_dz, s->planck);
+  HIPCHK(hipGetLastError());
+  s->ca_have_B = planck != nullptr;
+  return TSX_OK;
+}
+
 // set_optical_properties (src/pprts.F90:1764-2000) on the device: delta scaling (:1903-1917), which layers are 1-D
 // (:669-677), their Eddington coefficients (:1962-1992), then the coefficient lookups.  Raw (unscaled) fields in.
 extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *albedo, const double *kabs, const double *ksca,
@@ -465,6 +589,9 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
   TsxLogScope log_scope(s, TSX_EV_SET_OPTPROP);  // set_optprop, src/pprts.F90:1785-2077
   const TsxGeo &gm = s->geo;
   const hipMemcpyKind mk = where == TSX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  if (s->collapse > 1) {
+    if ((rc = collapse_optprop(s, albedo, kabs, ksca, g, dz, planck, dx, ldelta_scaling, where))) return rc;
+  } else {
   if ((rc = keep_field(s, &s->d_kabs, kabs, (size_t)gm.Nc, where))) return rc;
   if ((rc = keep_field(s, &s->d_ksca, ksca, (size_t)gm.Nc, where))) return rc;
   if ((rc = keep_field(s, &s->d_g, g, (size_t)gm.Nc, where))) return rc;
@@ -514,11 +641,12 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
     hipLaunchKernelGGL(tsx_k_eddington, dim3(grid_for(gm.Nc)), dim3(TSX_BLOCK), 0, s->stream, gm, s->d_kabs, s->d_ksca, s->d_g,
                        s->d_dz, s->sun_costheta, s->l1d, s->a11, s->a12, s->a13, s->a23, s->a33);
   }
+  }
   if ((rc = ensure_coef_storage(s, 4))) return rc;
   if ((rc = lut_diffuse_launch(s, s->d_kabs, s->d_ksca, s->d_g, s->d_dz, dx))) return rc;
   HIPCHK(hipGetLastError());
   if (planck) {
-    if ((rc = keep_field(s, &s->planck, planck, (size_t)(gm.Nz + 1) * gm.ncol, where))) return rc;
+    if (s->collapse <= 1 && (rc = keep_field(s, &s->planck, planck, (size_t)(gm.Nz + 1) * gm.ncol, where))) return rc;
   } else if (s->planck) {
     HIPCHK(tsx_dev_free(s->planck));
     s->planck = nullptr;
@@ -632,6 +760,29 @@ extern "C" int tsx_pprts_zero_guess(tsx_solver *s) {
   }
   HIPCHK(hipStreamSynchronize(s->stream));
   return TSX_OK;
+}
+
+// init_pprts(..., collapseindex) (src/pprts.F90:213, 229, 849-853, 1067-1078): from the next tsx_pprts_set_optical_properties on,
+// the caller's fields describe Nz + c - 1 atmosphere layers and the top c of them are merged into solver layer 0.  A changed c is a
+// new atmosphere, as a new init_pprts would be: coefficients, stored solutions and the initial guess are dropped.
+extern "C" int tsx_pprts_set_collapse(tsx_solver *s, int32_t collapseindex) {
+  ARGCHK(s, "tsx_pprts_set_collapse: null");
+  const int c = collapseindex > 1 ? (int)collapseindex : 1;
+  if (c == s->collapse) return TSX_OK;
+  HIPCHK(hipSetDevice(s->device));
+  s->collapse = c;
+  s->have_optprop = s->have_coeffs = false;
+  s->dir_coeffs_valid = s->dir_seam = s->dir_seam_S = false;
+  s->pcx_valid = s->coef_h_valid = false;
+  s->ca_have_B = false;
+  s->dd_from_coords = false;  // no grouping is taken over from the other atmosphere's coefficients
+  s->pcr_have_R = 0;
+  slots_free(s);
+  s->cur_uid = 0;
+  s->have_solution = s->guess_foreign = false;
+  s->its_hint_cold = s->its_hint_warm = 0;
+  s->its_hint_key = 0;
+  return tsx_pprts_zero_guess(s);
 }
 
 __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_asum(long long n, const double *__restrict__ v, double *__restrict__ partials) {
@@ -778,7 +929,7 @@ static int pprts_solve_t(tsx_solver *s, double edirTOA, int lsolar, const tsx_ks
     if (first_of_uid && !opts->skip_complete_initial_run) {
       double rt, at;
       int32_t mx;
-      tsx_determine_ksp_tolerances(s, 1.0 - (double)s->n1d / (double)s->geo.Nz, &rt, &at, &mx);
+      tsx_determine_ksp_tolerances(s, tsx_unconstrained_fraction(s), &rt, &at, &mx);
       o.rtol = fmin(o.rtol, rt);
       o.atol = fmin(o.atol, at);
       o.maxit = o.maxit > mx ? o.maxit : mx;
@@ -787,7 +938,7 @@ static int pprts_solve_t(tsx_solver *s, double edirTOA, int lsolar, const tsx_ks
     tsx_ksp_opts d;
     tsx_default_ksp_opts(&d);
     int32_t mx;
-    tsx_determine_ksp_tolerances(s, 1.0 - (double)s->n1d / (double)s->geo.Nz, &d.rtol, &d.atol, &mx);
+    tsx_determine_ksp_tolerances(s, tsx_unconstrained_fraction(s), &d.rtol, &d.atol, &mx);
     d.maxit = mx;
     d.pc = TSX_PC_REDBLACK;
     d.pc_sweeps = 0;  // automatic, see prepare_ksp
@@ -815,14 +966,15 @@ static int pprts_solve_t(tsx_solver *s, double edirTOA, int lsolar, const tsx_ks
     // the blocks' column sums per distinct block, where blocks are shared (built here already: the solve needs them anyway)
     if ((rc = tsx_dedup_ensure(s))) return rc;
     const double *cs = s->dd_on ? s->dd_colsum : (const double *)nullptr;
+    const double *cB = s->collapse > 1 && s->ca_have_B ? s->ca_B : (const double *)nullptr;  // layer 0 of a collapsed atmosphere
     if (s->coef_bytes == 4)
       hipLaunchKernelGGL((tsx_k_setup_b_thermal<NTOP, NSIDE, float>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
                          (const float *)s->coef, s->l1d, s->a11, s->a12, s->albedo, s->planck, s->bsrfc, s->d_kabs, s->d_dz, s->opt_dx,
-                         s->opt_dy, s->vb, cs, s->dd_cidx, (long long)s->dd_nent);
+                         s->opt_dy, s->vb, cs, s->dd_cidx, (long long)s->dd_nent, cB);
     else
       hipLaunchKernelGGL((tsx_k_setup_b_thermal<NTOP, NSIDE, double>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
                          (const double *)s->coef, s->l1d, s->a11, s->a12, s->albedo, s->planck, s->bsrfc, s->d_kabs, s->d_dz, s->opt_dx,
-                         s->opt_dy, s->vb, (const double *)nullptr, (const int *)nullptr, 0ll);
+                         s->opt_dy, s->vb, (const double *)nullptr, (const int *)nullptr, 0ll, cB);
   }
   HIPCHK(hipGetLastError());
   }
@@ -967,7 +1119,22 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_export_cellfield(TsxGeo g, co
 
 extern "C" int tsx_pprts_get_field(tsx_solver *s, int which, double *out, int where) {
   ARGCHK(s && out, "tsx_pprts_get_field: null");
-  ARGCHK(which >= 0 && which <= 12, "tsx_pprts_get_field: which must be 0..12");
+  ARGCHK(which >= 0 && which <= 14, "tsx_pprts_get_field: which must be 0..14");
+  if (which >= 13) {  // atm%Btop / atm%Bbot of a collapsed atmosphere (src/pprts.F90:2192-2196), (xs:xe, ys:ye); NaN without them
+    HIPCHK(hipSetDevice(s->device));
+    const size_t nb = sizeof(double) * (size_t)s->geo.ncol;
+    if (s->collapse > 1 && s->ca_have_B && s->have_optprop) {
+      HIPCHK(hipMemcpyAsync(out, s->ca_B + (which == 14 ? s->geo.ncol : 0), nb,
+                            where == TSX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
+    } else if (where == TSX_HOST) {
+      std::vector<double> nan((size_t)s->geo.ncol, std::numeric_limits<double>::quiet_NaN());
+      memcpy(out, nan.data(), nb);
+    } else {
+      HIPCHK(hipMemsetAsync(out, 0xff, nb, s->stream));
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return TSX_OK;
+  }
   if (which >= 5) {  // what set_optical_properties derived on the device: delta-scaled properties, Eddington coefficients
     HIPCHK(hipSetDevice(s->device));
     const TsxGeo &gq = s->geo;

@@ -174,6 +174,7 @@ extern "C" int tsx_dir_set_coeffs(tsx_solver *s, const void *dir2dir, const void
                                   const double *a33, const double *a13, const double *a23, double dx, double dy, int where) {
   ARGCHK(s && dir2dir && l1d, "tsx_dir_set_coeffs: null argument");
   ARGCHK(coeff_kind == 4 || coeff_kind == 8, "tsx_dir_set_coeffs: coeff_kind must be 4 or 8");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_dir_set_coeffs")) return rc_c;
   ARGCHK(dx > 0 && dy > 0, "tsx_dir_set_coeffs: dx, dy must be positive");
   if (!s->have_sun) {
     tsx_set_error("tsx_dir_set_coeffs: call tsx_pprts_set_angles first (the sweep order and the coefficients depend on the sun)");
@@ -311,6 +312,7 @@ static int seam_b_solar_t(tsx_solver *s, double *b_dev) {
 }
 extern "C" int tsx_setup_b_solar(tsx_solver *s, const void *edir, const double *albedo, void *b, int vec_kind, int where) {
   ARGCHK(s && b, "tsx_setup_b_solar: null argument");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_setup_b_solar")) return rc_c;
   if (!s->dir_coeffs_valid || !s->dir_seam || !s->dir_seam_S) {
     tsx_set_error("tsx_setup_b_solar: call tsx_dir_set_coeffs with dir2diff first");
     return TSX_ERR_STATE;
@@ -353,11 +355,11 @@ static int seam_b_thermal_t(tsx_solver *s, double *b_dev) {
   if (s->coef_bytes == 4)
     hipLaunchKernelGGL((tsx_k_setup_b_thermal<NTOP, NSIDE, float>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
                        (const float *)s->coef, s->l1d, s->a11, s->a12, s->albedo, s->planck, s->bsrfc, s->d_kabs, s->d_dz, s->opt_dx,
-                       s->opt_dy, s->vb, cs, s->dd_cidx, (long long)s->dd_nent);
+                       s->opt_dy, s->vb, cs, s->dd_cidx, (long long)s->dd_nent, (const double *)nullptr);
   else
     hipLaunchKernelGGL((tsx_k_setup_b_thermal<NTOP, NSIDE, double>), dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g,
                        (const double *)s->coef, s->l1d, s->a11, s->a12, s->albedo, s->planck, s->bsrfc, s->d_kabs, s->d_dz, s->opt_dx,
-                       s->opt_dy, s->vb, (const double *)nullptr, (const int *)nullptr, 0ll);
+                       s->opt_dy, s->vb, (const double *)nullptr, (const int *)nullptr, 0ll, (const double *)nullptr);
   HIPCHK(hipGetLastError());
   return export_vec<NTOP, NSIDE>(s, s->vb, b_dev);
 }
@@ -365,6 +367,7 @@ extern "C" int tsx_setup_b_thermal(tsx_solver *s, const double *planck, const do
                                    const double *dz, double dx, double dy, void *b, int vec_kind, int where) {
   ARGCHK(s && planck && kabs && dz && b, "tsx_setup_b_thermal: null argument");
   ARGCHK(dx > 0 && dy > 0, "tsx_setup_b_thermal: dx, dy must be positive");
+  if (int rc_c = tsx_refuse_collapsed(s, "tsx_setup_b_thermal")) return rc_c;
   if (!s->have_coeffs) {
     tsx_set_error("tsx_setup_b_thermal: call tsx_diff_set_coeffs first (emissivities come from the diffuse blocks, a11 / a12 and the albedo)");
     return TSX_ERR_STATE;

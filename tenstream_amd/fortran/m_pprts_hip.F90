@@ -22,7 +22,7 @@ module m_pprts_hip
     & tsx_comm_unique_id, tsx_comm_init, tsx_comm_set_callbacks, tsx_determine_ksp_tolerances, tsx_default_ksp_opts, &
     & tsx_lut_set_diffuse, tsx_lut_load_diffuse_mmap4, tsx_lut_set_direct, tsx_lut_load_direct_mmap4, &
     & tsx_diff_set_optprop, tsx_diff_get_coeffs, &
-    & tsx_pprts_set_angles, tsx_pprts_set_direct_tolerances, tsx_pprts_set_optical_properties, tsx_pprts_set_optprop, &
+    & tsx_pprts_set_angles, tsx_pprts_set_collapse, tsx_pprts_set_direct_tolerances, tsx_pprts_set_optical_properties, tsx_pprts_set_optprop, &
     & tsx_pprts_solve, tsx_pprts_zero_guess, tsx_pprts_select_solution, tsx_pprts_get_result, tsx_pprts_get_field, &
     & TSX_HOST, TSX_DEVICE, TSX_PC_NONE, TSX_PC_COLUMN, TSX_PC_ZEBRA, TSX_PC_REDBLACK
 
@@ -296,6 +296,14 @@ module m_pprts_hip
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: handle
       real(c_double), value :: phi0, theta0
+      integer(c_int) :: ierr
+    end function
+    !> init_pprts' collapseindex (src/pprts.F90:213, 1067-1078): after tsx_pprts_set_angles; with c > 1 the optical
+    !> properties have Nz + c - 1 layers and the top c of them become solver layer 0 (include/tsx.h)
+    function tsx_pprts_set_collapse(handle, collapseindex) bind(C, name='tsx_pprts_set_collapse') result(ierr)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: collapseindex
       integer(c_int) :: ierr
     end function
     function tsx_pprts_set_direct_tolerances(handle, rtol, atol, maxit) bind(C, name='tsx_pprts_set_direct_tolerances') result(ierr)

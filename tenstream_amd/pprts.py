@@ -55,20 +55,77 @@ def eddington_coeff_ec(dtau, w0, g, mu0):
     return t, r, rdir, sdir, tdir
 
 
+def adding(a11, a12, a13, a23, a33, dtau=None, planck=None):
+    """adding (src/pprts.F90:2125-2198) over the first axis (layers, top first), vectorised over the others, with a21 = a12 and
+    a22 = a11 (:2072-2073).  Returns the merged (a11 = Tbot, a12 = Rtop, a13 = rdir, a23 = sdir, a33 = tdir) and, with dtau and
+    planck (levels), (Btop, Bbot) of schwarzschild(2, dtau, 0, ..., opt_srfc_emission=0) (src/schwarzschild.F90:82-135)."""
+    N = a11.shape[0]
+    t, r, tdir, rdir, sdir = a11[0], a12[0], a33[0], a13[0], a23[0]
+    for k in range(1, N):
+        rl, tl = r, t
+        r = r + (a12[k] * (t * t)) / (1.0 - r * a12[k])
+        t = t * a11[k] / (1.0 - rl * a12[k])
+        sdir = (a11[k] * sdir + tdir * a13[k] * rl * a11[k]) / (1.0 - rl * a12[k]) + tdir * a23[k]
+        rdir = rdir + (tdir * a13[k] + sdir * a12[k]) * tl
+        tdir = tdir * a33[k]
+    rtop = r
+    t, r = a11[N - 1], a12[N - 1]
+    for k in range(N - 2, -1, -1):
+        rl = r
+        r = a12[k] + (r * (a11[k] * a11[k])) / (1.0 - r * a12[k])
+        t = t * a11[k] / (1.0 - rl * a12[k])
+    merged = (t, rtop, rdir, sdir, tdir)
+    if planck is None:
+        return merged, None
+
+    def rad(tau, bn, bf, L):  # schwarzschild_radiance (src/schwarzschild.F90:69-80)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tm1 = np.expm1(-tau)
+            thick = L * (tm1 + 1) + (bf - bn) - (bn - (bf - bn) / tau) * tm1
+        return np.where(tau > 1e-3, thick, (bn + bf) * .5 * tau + L * (1.0 - tau))
+
+    edn = eup = 0.0
+    for mu in (0.5 - 0.5 / np.sqrt(3.0), 0.5 + 0.5 / np.sqrt(3.0)):
+        L = 0.0
+        for k in range(N):
+            L = rad(dtau[k] / mu, planck[k], planck[k + 1], L)
+        edn = edn + L * mu * 0.5
+        L = 0.0
+        for k in range(N - 1, -1, -1):
+            L = rad(dtau[k] / mu, planck[k + 1], planck[k], L)
+        eup = eup + L * mu * 0.5
+    return merged, (eup * 2 * np.pi / np.pi, edn * 2 * np.pi / np.pi)
+
+
 class PprtsSolver:
     """One pprts solver (3_10) on one GPU, driven like the reference's Fortran/C API."""
 
-    def __init__(self, Nz, Nx, Ny, dx, dy, phi0, theta0, solver="3_10", device=-1, **decomposition):
+    def __init__(self, Nz, Nx, Ny, dx, dy, phi0, theta0, solver="3_10", device=-1, collapseindex=1, **decomposition):
         """Nx, Ny: the columns this rank owns; decomposition: xs, ys, glob_xm, glob_ym, rank, nranks, neighbors (W, E, S, N)
         as DiffuseSolver takes them (several ranks: call core.comm_init / core.comm_set_callbacks before the first
-        set_optical_properties), force_halo for tests."""
-        self.Nz, self.Nx, self.Ny, self.dx, self.dy = int(Nz), int(Nx), int(Ny), float(dx), float(dy)
-        self.core = DiffuseSolver(solver, Nz, Nx, Ny, device=device, **decomposition)
+        set_optical_properties), force_halo for tests.  collapseindex as init_pprts takes it (src/pprts.F90:213, 1067-1078):
+        Nz is the atmosphere's layer count, and with collapseindex = c > 1 the top c layers are merged into one, so that the
+        solver (self.Nz, the results) has Nz - c + 1 layers (tsx_pprts_set_collapse)."""
+        c = max(int(collapseindex), 1)
+        self.Nz_atm, self.collapse = int(Nz), c
+        self.Nz, self.Nx, self.Ny, self.dx, self.dy = int(Nz) - c + 1, int(Nx), int(Ny), float(dx), float(dy)
+        if self.Nz < 1:
+            raise ValueError(f"collapseindex {c} leaves no layer of the {Nz}")
+        self.core = DiffuseSolver(solver, self.Nz, Nx, Ny, device=device, **decomposition)
         self.lib = self.core.lib
         self.h = self.core.h
         self.phi0, self.theta0 = float(phi0), float(theta0)
         _lib.check(self.lib.tsx_pprts_set_angles(self.h, self.phi0, self.theta0))
         self.mu0 = max(np.cos(np.deg2rad(theta0)), 0.0) if theta0 < 90 else 0.0
+        if c > 1:
+            _lib.check(self.lib.tsx_pprts_set_collapse(self.h, c))
+
+    def set_collapse(self, collapseindex):
+        """tsx_pprts_set_collapse on this handle: the solver keeps its self.Nz layers, the next set_optical_properties takes
+        self.Nz + c - 1 atmosphere layers.  A changed c drops the coefficients and the stored solutions."""
+        c = max(int(collapseindex), 1)
+        _lib.check(self.lib.tsx_pprts_set_collapse(self.h, int(collapseindex)))
+        self.collapse, self.Nz_atm, self._fields = c, self.Nz + c - 1, None
 
     # -- look-up tables ------------------------------------------------------------------------------
     def set_lut_diffuse(self, table, axes):
@@ -84,14 +141,14 @@ class PprtsSolver:
 
     # -- set_optical_properties ------------------------------------------------------------------------
     def set_optical_properties(self, albedo, kabs, ksca, g, dz, planck=None, ldelta_scaling=True, planck_srfc=None):
-        """Fields (Ny, Nx, Nz) float64 (numpy, or CUDA tensors to stay on the device), k = 0 at TOA; albedo scalar or
-        (Ny, Nx); planck (Ny, Nx, Nz+1) or None; planck_srfc scalar or (Ny, Nx) or None: the surface's own Planck emission
+        """Fields (Ny, Nx, Nz) float64 (numpy, or CUDA tensors to stay on the device), k = 0 at TOA, Nz = self.Nz_atm (the
+        atmosphere's layers; self.Nz + collapseindex - 1 with collapse); albedo scalar or (Ny, Nx); planck (Ny, Nx, Nz+1) or None; planck_srfc scalar or (Ny, Nx) or None: the surface's own Planck emission
         (atm%Bsrfc, src/pprts.F90:1773, 1823-1829, used at :4958-4970).  Delta scaling, 1-D layer detection, Eddington coefficients and the
         coefficient lookups all run on the device (tsx_pprts_set_optical_properties)."""
         from .solver import _is_torch
 
         on_dev = _is_torch(kabs)
-        shape = (self.Ny, self.Nx, self.Nz)
+        shape = (self.Ny, self.Nx, self.Nz_atm)
         if on_dev:
             import torch
 
@@ -101,7 +158,7 @@ class PprtsSolver:
             f = lambda a, shp: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shp))
         raw = dict(kabs=f(kabs, shape), ksca=f(ksca, shape), g=f(g, shape), dz=f(dz, shape),
                    albedo=f(albedo, (self.Ny, self.Nx)),
-                   planck=None if planck is None else f(planck, (self.Ny, self.Nx, self.Nz + 1)),
+                   planck=None if planck is None else f(planck, (self.Ny, self.Nx, self.Nz_atm + 1)),
                    planck_srfc=None if planck_srfc is None else f(planck_srfc, (self.Ny, self.Nx)))
         self._raw, self._ldelta, self._fields = raw, bool(ldelta_scaling), None
         ptr = lambda a: None if a is None else _ptr(a, np.float64)[0]
@@ -112,7 +169,8 @@ class PprtsSolver:
     @property
     def fields(self):
         """Host mirror of what the device derived (delta-scaled properties, Eddington coefficients): for tests and
-        diagnostics only, computed on demand from the raw inputs."""
+        diagnostics only, computed on demand from the raw inputs.  With collapse: the solver's layers, the atmosphere's at
+        atmk(k) = k + c - 1, layer 0 of a11..a33 merged by `adding`, and Btop / Bbot (Ny, Nx) with planck."""
         if self._fields is None:
             r = {k: (None if v is None else (v.cpu().numpy() if hasattr(v, "cpu") else v)) for k, v in self._raw.items()}
             kabs, ksca, g = (np.array(r[k], dtype=np.float64, copy=True) for k in ("kabs", "ksca", "g"))
@@ -120,23 +178,43 @@ class PprtsSolver:
                 kabs, ksca, g = delta_scale(kabs, ksca, g)
             ext = np.maximum(np.finfo(np.float64).tiny, kabs + ksca)
             a11, a12, a13, a23, a33 = eddington_coeff_ec(r["dz"] * ext, ksca / ext, g, self.mu0)
-            self._fields = dict(kabs=kabs, ksca=ksca, g=g, dz=r["dz"], a11=a11, a12=a12, a13=a13, a23=a23, a33=a33,
-                                albedo=r["albedo"], planck=r["planck"], planck_srfc=r["planck_srfc"])
+            F = dict(kabs=kabs, ksca=ksca, g=g, dz=r["dz"], a11=a11, a12=a12, a13=a13, a23=a23, a33=a33,
+                     albedo=r["albedo"], planck=r["planck"], planck_srfc=r["planck_srfc"])
+            c = self.collapse
+            if c > 1:
+                top = [np.moveaxis(F[n][:, :, :c], 2, 0) for n in ("a11", "a12", "a13", "a23", "a33")]
+                pl = None if F["planck"] is None else np.moveaxis(F["planck"][:, :, : c + 1], 2, 0)
+                merged, B = adding(*top, dtau=np.moveaxis((F["dz"] * kabs)[:, :, :c], 2, 0), planck=pl)
+                for n in ("kabs", "ksca", "g", "dz", "a11", "a12", "a13", "a23", "a33", "planck"):
+                    if F[n] is not None:
+                        F[n] = np.array(F[n][:, :, c - 1:])
+                for n, v in zip(("a11", "a12", "a13", "a23", "a33"), merged):
+                    F[n][:, :, 0] = v
+                F["Btop"], F["Bbot"] = (None, None) if B is None else B
+            self._fields = F
         return self._fields
 
     @property
-    def l1d(self):
-        """1-D layers as the reference flags them (src/pprts.F90:670-677, 708-719); host mirror of the device logic"""
+    def l1d_atm(self):
+        """1-D layers of the atmosphere as the reference flags them (src/pprts.F90:670-677; the top collapseindex layers forced,
+        :693-705; the count applied from the top, :708-719); host mirror of the device logic"""
         dz = self._raw["dz"]
         dz = dz.cpu().numpy() if hasattr(dz, "cpu") else dz
         ex = (dz / self.dx > TWOSTR_RATIO).any(axis=(0, 1))
-        l1d = np.zeros(self.Nz, dtype=np.uint8)
+        l1d = np.zeros(self.Nz_atm, dtype=np.uint8)
         l1d[-1] = ex[-1]
         upper = np.nonzero(ex[:-1])[0]
         if upper.size:
             l1d[: upper.max() + 1] = 1
+        if self.collapse > 1:
+            l1d[: self.collapse] = 1
         l1d[: int(l1d.sum())] = 1  # the count of 1-D layers is applied from the top (:708-719)
         return l1d
+
+    @property
+    def l1d(self):
+        """1-D flags of the solver's layers: the atmosphere's at atmk(k) = k + collapseindex - 1"""
+        return self.l1d_atm[self.collapse - 1:]
 
     # -- solve_pprts -------------------------------------------------------------------------------------
     def solve(self, edirTOA, lsolar=None, zero_guess=False, uid=None, **opts) -> KspInfo:
@@ -184,6 +262,7 @@ class PprtsSolver:
                   "dir2diff": (4, (self.Ny, self.Nx, self.Nz, S * D))}
         cell = (self.Ny, self.Nx, self.Nz)   # what the device derived in set_optical_properties (delta scaling, Eddington)
         shapes.update({n: (5 + q, cell) for q, n in enumerate(("kabs", "ksca", "g", "a11", "a12", "a13", "a23", "a33"))})
+        shapes.update(Btop=(13, (self.Ny, self.Nx)), Bbot=(14, (self.Ny, self.Nx)))   # collapse: atm%Btop / Bbot (:2192-2196)
         idx, shp = shapes[which]
         out = np.empty(shp)
         _lib.check(self.lib.tsx_pprts_get_field(self.h, idx, _ptr(out, np.float64)[0], 0))
