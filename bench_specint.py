@@ -52,6 +52,10 @@ def parse(argv=None):
     ap.add_argument("--pc-sweeps", type=int, default=0, help="0 = library default")
     ap.add_argument("--collapse", type=int, default=0, help="also run the loop with init_pprts' collapseindex = N (-1: every background "
                     "layer, n_bg as atm_ke counts them, src/tenstr_atm.F90:508-512) and report it beside the headline (not part of it)")
+    ap.add_argument("--solver-1d", choices=("twostream", "schwarzschild"), default=None, help="also run the loop on handles that answer "
+                    "every g-point with the 1-D column solver (tsx_pprts_set_1d_solver); reported beside the headline")
+    ap.add_argument("--guess-2str", action="store_true", help="also run the loop with -initial_guess_from_2str at the first solve of "
+                    "every uid (tsx_pprts_guess_from_2str); reported beside the headline")
     ap.add_argument("--phi0", type=float, default=180.0)
     ap.add_argument("--theta0", type=float, default=40.0)
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (the oracle's restatement of the reference's "
@@ -68,7 +72,7 @@ def column_dz(Nz, n_bg, dz_dyn=50.0):
     return dz
 
 
-def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
+def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1, solver_1d=None, guess_2str=False):
     import torch
 
     from tenstream_amd import lut as LUT
@@ -109,7 +113,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
     Tdir, Sdir = LUT.synthetic_direct_tables(dax)
     Ps = []
     for _ in range(K):
-        Pk = PprtsSolver(Nz, Nx, Ny, dx, dx, args.phi0, args.theta0, device=dev.index, collapseindex=collapse)
+        Pk = PprtsSolver(Nz, Nx, Ny, dx, dx, args.phi0, args.theta0, device=dev.index, collapseindex=collapse, solver_1d=solver_1d)
         Pk.set_lut_diffuse(LUT.synthetic_diffuse_table("3_10"), LUT.diffuse_axes("3_10"))
         Pk.set_lut_direct(Tdir, Sdir, dax)
         Ps.append(Pk)
@@ -133,6 +137,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
     tstreams = [torch.cuda.Stream(device=dev) for _ in range(K)] if K > 1 else [None]
     mu0 = float(np.cos(np.deg2rad(args.theta0)))
     shift = {"n": 0}
+    guessed = set()   # --guess-2str: the uids whose first solve has had its two-stream guess
 
     def run(q, w=0):
         P, tmp, acc = Ps[w], tmps[w], accs[w]
@@ -143,7 +148,13 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
                                  planck_srfc=None if lsolar else planck_srfc0 * weights[q])
         kw = dict(pc_sweeps=args.pc_sweeps) if args.pc_sweeps > 0 else {}
         e0 = 1361.0 * weights[q] if lsolar else 0.0
-        info = P.solve(e0, lsolar=lsolar, uid=q, **kw)
+        if guess_2str and q not in guessed:
+            guessed.add(q)
+            P.solve_select(q)
+            P.guess_from_2str(e0, lsolar=lsolar)
+            info = P.solve(e0, lsolar=lsolar, **kw)
+        else:
+            info = P.solve(e0, lsolar=lsolar, uid=q, **kw)
         P.get_result(out=tmp)
         for a, t in zip(acc, tmp):
             a += t
@@ -269,7 +280,7 @@ def run_loop(args, dev, rank=0, world=1, all_reduce=None, collapse=1):
         except Exception as e:   # noqa: BLE001
             roofline = {"error": str(e)}
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and args.sw > 0 and collapse == 1:
+    if rank == 0 and not args.no_cpu_baseline and args.sw > 0 and collapse == 1 and solver_1d is None and not guess_2str:
         # CPU baseline, one g-point (the solar one with the median optical-depth factor): the very diffuse system the device
         # solved -- its blocks, 1-D layers, Eddington coefficients and right-hand side read back -- through the oracle's
         # restatement of the reference's default CPU path (assembled AIJ + FBCGS + PCBJACOBI / ILU(0), one subdomain per usable
@@ -339,6 +350,18 @@ def main():
                               "seconds": sc[-1], "calls": [dict(cc, seconds=s_, gpoints_per_s=R["ng"] / s_) for cc, s_ in zip(Rc["calls"], sc)],
                               "breakdown": Rc["breakdown"], "note": "reported only: init_pprts' collapseindex merges the top layers into "
                                                                     "one (tsx_pprts_set_collapse); the headline is the uncollapsed loop"}}
+    for key, kwl, note in (("solver_1d", dict(solver_1d=args.solver_1d) if args.solver_1d else None,
+                            "reported only: every g-point answered by the 1-D column solver (tsx_pprts_set_1d_solver), no LUT lookups, no "
+                            "Krylov loop"),
+                           ("guess_2str", dict(guess_2str=True) if args.guess_2str else None,
+                            "reported only: -initial_guess_from_2str at the first solve of every uid (tsx_pprts_guess_from_2str); off by default")):
+        if kwl is None:
+            continue
+        Rl = run_loop(args, dev, rank, world, all_reduce=(dist.all_reduce if world > 1 else None), **kwl)
+        sl = seconds(Rl)
+        extra[key] = dict(kwl, value=R["ng"] / sl[-1], unit="g-points/s", seconds=sl[-1],
+                          calls=[dict(cc, seconds=s_, gpoints_per_s=R["ng"] / s_) for cc, s_ in zip(Rl["calls"], sl)],
+                          breakdown=Rl["breakdown"], note=note)
     if rank == 0:
         Nx, Ny, Nz, ng = args.nx, args.ny, args.nz, R["ng"]
         last = len(secs) - 1

@@ -336,6 +336,35 @@ int tsx_pprts_set_optprop(tsx_solver *s, const double *kabs, const double *ksca,
  * (src/pprts.F90:2542-2558) unless tsx_pprts_zero_guess was called. */
 int tsx_pprts_solve(tsx_solver *s, double edirTOA, int lsolar, const tsx_ksp_opts *opts, tsx_ksp_result *res);
 int tsx_pprts_zero_guess(tsx_solver *s);
+/* The 1-D routes of solve_pprts (src/pprts.F90:2627-2638; src/pprts_1D_solvers.F90:55-252 twostream, :418-582 schwarz): with a mode
+ * on, the handle is a t_solver_2str.  tsx_pprts_set_optical_properties then needs no LUT (src/pprts.F90:536) and only keeps the
+ * delta-scaled fields of the atmosphere's Nz + c - 1 layers; tsx_pprts_solve runs one lane per column instead of the direct sweep and
+ * the Krylov loop: delta_eddington_twostream (src/twostream.F90:50-184; without planck its adding form, :335-390) with
+ * dtau = dz (kabs + ksca), w0 = ksca / max(kext, eps), mu0 = sun%mu and incSolar = edirTOA (both 0 for thermal), or -- mode
+ * TSX_1D_SCHWARZSCHILD and a thermal solve, as under -schwarzschild (:2629-2632) -- schwarzschild with dtau = dz kabs and nmu
+ * Gauss-Legendre nodes on (0, 1) (src/schwarzschild.F90:81-135, use_legendre; -schwarzschild_Nmu, default 2, 1..16 accepted).  A solar
+ * solve runs twostream in either mode.  A thermal solve without planck returns TSX_ERR_STATE.  The solve exchanges nothing and
+ * reduces nothing, whatever the decomposition.  It fills tsx_ksp_result with niter = 0, no residuals, the device time, and
+ * reason = TSX_REASON_1D_TWOSTREAM or TSX_REASON_1D_SCHWARZSCHILD (positive like PETSc's converged reasons, outside their range).
+ * tsx_pprts_get_result returns the stored W/m2 fluxes -- level 0 the atmosphere's level 0, level k >= 1 its level atmk(0) + k -- and
+ * abso(k) = (Edn(a) - Edn(a+1) - Eup(a) + Eup(a+1) [+ S(a) - S(a+1)]) / dz(a), a = atmk(k) (src/pprts_1D_solvers.F90:201-233), times
+ * sun%mu when solar (src/pprts.F90:5883-5888); no flux divergence is computed (lchanged = .false., :245).  tsx_pprts_select_solution
+ * parks and restores such solutions (as real64).  tsx_pprts_get_field 0..4, tsx_pprts_set_optprop and tsx_pprts_guess_from_2str
+ * return TSX_ERR_STATE on such a handle, tsx_diff_* as on any handle without coefficients.  A changed mode drops coefficients,
+ * optical properties, stored solutions and the initial guess, like tsx_pprts_set_collapse; nmu outside 1..16: TSX_ERR_ARG. */
+#define TSX_1D_OFF 0
+#define TSX_1D_TWOSTREAM 1
+#define TSX_1D_SCHWARZSCHILD 2
+#define TSX_REASON_1D_TWOSTREAM 101
+#define TSX_REASON_1D_SCHWARZSCHILD 102
+int tsx_pprts_set_1d_solver(tsx_solver *s, int32_t mode, int32_t nmu);
+/* -initial_guess_from_2str (src/pprts.F90:2560-2567), as an explicit call like tsx_pprts_zero_guess: twostream on the optical
+ * properties the handle holds (3_10 or 8_16, with or without collapse, mode TSX_1D_OFF), then every top-face diffuse dof of a level
+ * gets Edn or Eup by is_inward times area_divider / streams, every top-face direct dof S times area_divider / streams
+ * (src/pprts_1D_solvers.F90:201-218), scaled from W/m2 to W as scale_flx(lWm2 = .false.) does (src/pprts.F90:3901-3987); the side
+ * dofs keep the zero of :108.  The next tsx_pprts_solve starts from it, as the first solve of its uid.  Needs
+ * tsx_pprts_set_optical_properties; thermal needs planck. */
+int tsx_pprts_guess_from_2str(tsx_solver *s, double edirTOA, int lsolar);
 /* solve_pprts(..., opt_solution_uid) (src/pprts.F90:2487-2558; get_solution_uid): make `uid` the solution the next
  * tsx_pprts_solve works on.  The current solution is parked under its own uid (as real32; the reference's
  * lcompress_solutions does the like); the initial guess becomes uid's previous solution, or, for a uid never solved, the
@@ -411,7 +440,8 @@ int tsx_probe_bandwidth(tsx_solver *s, size_t bytes, int reps, double *out4);
  * per event a count and the DEVICE time between two HIP events recorded on the solver's stream around it, and a roctx range of the same
  * name around the host code (rocprofv3 --marker-trace shows a spectral loop g-point by g-point; roctx is bound at run time, absent = no
  * ranges).  Off by default (no event records on the hot path); tsx_log_enable(s, 1) or TSX_LOG=1 at tsx_create switch it on.
- * tsx_log_get synchronises the stream and fills up to *nevents = 11 entries; names[] point to static strings; any array may be null. */
+ * solve_twostream and solve_schwarzschild (:2564-2566, 2630-2636) are listed after those once they have fired.
+ * tsx_log_get synchronises the stream and fills *nevents <= 13 entries; names[] point to static strings; any array may be null. */
 int tsx_log_enable(tsx_solver *s, int on);
 int tsx_log_get(tsx_solver *s, int32_t *nevents, const char **names, int64_t *counts, double *ms);
 

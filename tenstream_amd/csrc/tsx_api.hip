@@ -298,7 +298,7 @@ extern "C" int tsx_destroy(tsx_solver *s) {
                   s->vv,    s->vs,    s->vt,    s->stage_a, s->stage_b, s->sendW, s->sendE, s->sendS, s->sendN, s->recvW,
                   s->recvE, s->recvS, s->recvN, s->partials, s->scal, s->vw, s->pc_tmp, s->lut_diff.d_axes, s->lut_diff.d_table,
                   s->lut_T.d_axes, s->lut_T.d_table, s->lut_S.d_axes, s->lut_S.d_table, s->dirT, s->dirS, s->d_kabs, s->d_ksca,
-                  s->d_g, s->d_dz, s->a13, s->a23, s->a33, s->planck, s->bsrfc, s->edir_a, s->edir_b, s->dsc, s->abso, s->cell_samp, s->dd_colsum, s->pcx_rec, s->pcx_vz, s->flow_state, s->flow_prog, s->flow_zb8, s->flow_pr_dev, s->ca_buf, s->ca_B};
+                  s->d_g, s->d_dz, s->a13, s->a23, s->a33, s->planck, s->bsrfc, s->edir_a, s->edir_b, s->dsc, s->abso, s->cell_samp, s->dd_colsum, s->pcx_rec, s->pcx_vz, s->flow_state, s->flow_prog, s->flow_zb8, s->flow_pr_dev, s->ca_buf, s->ca_B, s->od_buf, s->od_flux};
   for (void *p : ptrs)
     if (p) (void)tsx_dev_free(p);
   if (s->vph && s->vph != s->vp) (void)tsx_dev_free(s->vph);
@@ -1846,9 +1846,9 @@ extern "C" int tsx_probe_bandwidth(tsx_solver *s, size_t bytes, int reps, double
 
 // ---- log events + roctx ranges (TsxLog, tsx_internal.hpp).  roctx comes from librocprofiler-sdk-roctx (ROCm 7; libroctx64 before
 // it), bound at run time on first use: libtsx links neither, and without the library the ranges are no-ops.
-static const char *const kLogNames[TSX_EV_COUNT] = {"set_optprop", "get_coeff_diff2diff", "get_coeff_dir2dir", "compute_Edir", "solve_Mdir",
+static const char *const kLogNames[TSX_EV_TOTAL] = {"set_optprop", "get_coeff_diff2diff", "get_coeff_dir2dir", "compute_Edir", "solve_Mdir",
                                                    "setup_diff_src", "compute_Ediff", "setup_Mdiff", "solve_Mdiff", "compute_absorption",
-                                                   "get_result"};
+                                                   "get_result", "solve_twostream", "solve_schwarzschild"};
 struct TsxRoctx {
   int (*push)(const char *) = nullptr;
   int (*pop)() = nullptr;
@@ -1939,11 +1939,15 @@ extern "C" int tsx_log_get(tsx_solver *s, int32_t *nevents, const char **names, 
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream));
   tsx_log_retire(s, true);
-  for (int q = 0; q < TSX_EV_COUNT; ++q) {
-    if (names) names[q] = kLogNames[q];
-    if (counts) counts[q] = s->log->count[q];
-    if (ms) ms[q] = s->log->ms[q];
+  int n = 0;
+  for (int q = 0; q < TSX_EV_TOTAL; ++q) {
+    if (q >= TSX_EV_COUNT && s->log->count[q] == 0) continue;  // the 1-D solvers' events: listed once they have fired
+    if (names) names[n] = kLogNames[q];
+    if (counts) counts[n] = s->log->count[q];
+    if (ms) ms[n] = s->log->ms[q];
+    ++n;
   }
+  *nevents = n;
   return TSX_OK;
 }
 

@@ -32,6 +32,8 @@ struct F2cState {
   double dx = 0, dy = 0, phi0 = 0, theta0 = 0;
   std::vector<double> dz1d;
   bool have_planck = false;
+  int mode_1d = TSX_1D_OFF;  // t_solver_2str (SOLVER_ID_PPRTS_2STR) / -schwarzschild: every solve is answered by the 1-D column solver
+  int solved_kind = -1;      // kind of radiation (lsolar) of the solution held; -1: none yet (-initial_guess_from_2str)
 };
 F2cState g_st;
 
@@ -73,6 +75,9 @@ void bcast0(double *v, size_t n) {
 //   -<solar|thermal>_diff_explicit                               (src/pprts.F90:2795-2801)
 //   -solar_dir_ksp_rtol / _ksp_atol / _ksp_max_it                (explicit_edir, src/pprts_explicit.F90:94-112)
 //   -accept_incomplete_solve                                     (src/pprts.F90:4271-4273)
+//   -schwarzschild, -schwarzschild_Nmu                           (src/tenstream_options.F90:130, src/pprts_1D_solvers.F90:486)
+//   -initial_guess_from_2str                                     (src/pprts.F90:2560-2567; the f2c solvers' prefix is empty,
+//                                                                 src/pprts_base.F90:224, so the bare and the prefixed key are one)
 struct Opt {
   std::string key, val;
 };
@@ -283,11 +288,15 @@ extern "C" void pprts_f2c_init(int fcomm, int *solver_id, int *Nz, int *Nx, int 
     for (int k = 0; k <= *Nz; ++k) ohhl[k] = (double)hhl[k];
   bcast0(ohhl.data(), ohhl.size());
 
-  if (*solver_id != TSX_SOLVER_3_10 && *solver_id != TSX_SOLVER_8_16)  // SOLVER_ID_PPRTS_3_10 / _8_16, f2c_solver_ids.h
-    die("solver_id " + std::to_string(*solver_id) + ": this back-end serves 3_10 (310) and 8_16 (816)");
+  const int id_2str = 2;  // SOLVER_ID_PPRTS_2STR, f2c_solver_ids.h
+  if (*solver_id != TSX_SOLVER_3_10 && *solver_id != TSX_SOLVER_8_16 && *solver_id != id_2str)  // SOLVER_ID_PPRTS_3_10 / _8_16
+    die("solver_id " + std::to_string(*solver_id) + ": this back-end serves 2str (2), 3_10 (310) and 8_16 (816)");
   if (*collapseindex > 1) die("collapseindex > 1 is not supported by this back-end");
   F2cState &st = g_st;
   st.solver_id = *solver_id;
+  st.solved_kind = -1;
+  // -schwarzschild for any solver id (thermal solves run schwarz, solar ones twostream), else twostream for a 2str solver
+  st.mode_1d = opt_bool("schwarzschild", false) ? TSX_1D_SCHWARZSCHILD : (*solver_id == id_2str ? TSX_1D_TWOSTREAM : TSX_1D_OFF);
   st.Nz = *Nz;
   st.Nx = *Nx;
   st.Ny = *Ny;
@@ -309,7 +318,7 @@ extern "C" void pprts_f2c_init(int fcomm, int *solver_id, int *Nz, int *Nx, int 
   st.ym = ((yi + 1) * st.gNy) / nyp - st.ys;
   tsx_grid grid;
   memset(&grid, 0, sizeof(grid));
-  grid.solver_id = st.solver_id;
+  grid.solver_id = st.solver_id == id_2str ? TSX_SOLVER_3_10 : st.solver_id;  // a 2str solver's results need no stream layout: 3_10's
   grid.Nz = st.Nz;
   grid.xm = st.xm;
   grid.ym = st.ym;
@@ -327,6 +336,12 @@ extern "C" void pprts_f2c_init(int fcomm, int *solver_id, int *Nz, int *Nx, int 
   chk(tsx_create(&grid, &st.h), "tsx_create");
   if (g_comm.nranks > 1) chk(tsx_comm_set_callbacks(st.h, g_comm.exchange, g_comm.allreduce, g_comm.ctx), "tsx_comm_set_callbacks");
   chk(tsx_pprts_set_angles(st.h, st.phi0, st.theta0), "tsx_pprts_set_angles");
+  if (st.mode_1d != TSX_1D_OFF) {  // "dont need LUT, we just compute Twostream anyway" (src/pprts.F90:536)
+    double nmu = 2;
+    opt_real("schwarzschild_Nmu", &nmu);
+    chk(tsx_pprts_set_1d_solver(st.h, st.mode_1d, (int32_t)nmu), "tsx_pprts_set_1d_solver");
+    return;
+  }
   load_luts(st.h, st.solver_id);
 }
 
@@ -398,6 +413,15 @@ extern "C" void pprts_f2c_solve(int fcomm, float edirTOA) {
   bcast0(&e, 1);
   const int lsolar = e > 0;  // lthermal = .not. lsolar, f2c_pprts.F90:340-341
   tsx_ksp_result res;
+  if (g_st.mode_1d != TSX_1D_OFF) {  // src/pprts.F90:2627-2638
+    chk(tsx_pprts_solve(g_st.h, e, lsolar, nullptr, &res), "tsx_pprts_solve");
+    return;
+  }
+  // -initial_guess_from_2str: at the first solve of the solution (this ABI has one, uid 0), inside `.not. solution%lset`
+  // (src/pprts.F90:2532-2567); a later change of the kind of radiation prepares the solution anew without a guess (:2578-2582)
+  if (g_st.solved_kind < 0 && opt_bool("initial_guess_from_2str", false))
+    chk(tsx_pprts_guess_from_2str(g_st.h, e, lsolar), "tsx_pprts_guess_from_2str");
+  g_st.solved_kind = lsolar;
   // tolerances and solver choice as the options database gives them (defaults: determine_ksp_tolerances, FBCGS)
   const std::string pre = lsolar ? "solar_diff_" : "thermal_diff_";
   tsx_ksp_opts o;

@@ -192,4 +192,11 @@ int tsx_records_share(tsx_solver *s, int R, const uint4 *P);
 // the red-black passes on the exact blocks with fp64 iterates, as a segmented scan (tsx_pcx.hip): what fp32_directions = 0 gets
 bool tsx_pcx_eligible(const tsx_solver *s);
 int tsx_pcx_apply(tsx_solver *s, const double *v, double *z, const int *done);
+// the 1-D column solvers (tsx_1d.hip): twostream / schwarz for every column into s->od_flux; that solution out to the result arrays
+// (device pointers); a twostream result into solution storage x / E as the 3-D solve's initial guess
+int tsx_1d_run(tsx_solver *s, double edirTOA, int lsolar, int schwarz);
+int tsx_1d_result(tsx_solver *s, int lsolar, double *redn, double *reup, double *rabso, double *redir);
+int tsx_1d_scatter(tsx_solver *s, int lsolar, double dx, double dy, double *x, double *E);
+size_t tsx_1d_solution_doubles(const tsx_solver *s);
+void tsx_gauss_legendre_01(int n, double *mu, double *w);
 int tsx_dedup_hash_buffer(tsx_solver *s, unsigned long long **h);

@@ -69,6 +69,7 @@ struct TsxSolSlot {  // one stored solution (initial guess of the next solve wit
   float *x32;    // diffuse streams, internal layout, N values
   float *e32;    // direct streams, S planes of (Nz+1)*ncol values (null if the slot never held a solar solution)
   int lsolar;
+  double *od = nullptr;  // a 1-D solution (tsx_1d.hip: S / Edn / Eup on the atmosphere's levels + the absorption), real64
 };
 
 struct TsxPeer;  // tsx_peer.hip
@@ -278,6 +279,14 @@ struct tsx_solver {
   int ca_nz_cap = 0;          // ... sized for this many atmosphere layers
   double *ca_B = nullptr;     // [2][ncol]: atm%Btop, atm%Bbot (:2192-2196); NaN without planck
   bool ca_have_B = false;
+  // 1-D column solvers (tsx_1d.hip; tsx_pprts_set_1d_solver, tsx_pprts_guess_from_2str)
+  int mode_1d = 0;            // TSX_1D_OFF / TSX_1D_TWOSTREAM / TSX_1D_SCHWARZSCHILD
+  int od_nmu = 2;             // Gauss-Legendre nodes of schwarz (-schwarzschild_Nmu)
+  double *od_buf = nullptr;   // cell-indexed planes of the layer-local terms + the recurrences' per-level temporaries (grow-only)
+  size_t od_cap = 0;          // ... in doubles
+  double *od_flux = nullptr;  // the 1-D solution: S, Edn, Eup [(Nz + c) * ncol] in W/m2, abso [Nz * ncol] in W/m3 (grow-only)
+  size_t od_flux_cap = 0;
+  bool sol_is_1d = false;     // the current solution is od_flux (lWm2 = .true., lchanged = .false.), not vx / edir_a
   TsxLog *log = nullptr;     // the reference's log events for this path + roctx ranges (tsx_log_enable; off: null)
 };
 
@@ -295,12 +304,14 @@ static inline double tsx_unconstrained_fraction(const tsx_solver *s) {
 enum TsxLogEvent {
   TSX_EV_SET_OPTPROP = 0, TSX_EV_GET_COEFF_DIFF2DIFF, TSX_EV_GET_COEFF_DIR2DIR, TSX_EV_COMPUTE_EDIR, TSX_EV_SOLVE_MDIR,
   TSX_EV_SETUP_DIFF_SRC, TSX_EV_COMPUTE_EDIFF, TSX_EV_SETUP_MDIFF, TSX_EV_SOLVE_MDIFF, TSX_EV_COMPUTE_ABSORPTION, TSX_EV_GET_RESULT,
-  TSX_EV_COUNT
+  TSX_EV_COUNT,  // the events of a 3-D g-point, always listed; the ones below only once they have fired
+  TSX_EV_SOLVE_TWOSTREAM = TSX_EV_COUNT, TSX_EV_SOLVE_SCHWARZSCHILD,  // solve_twostream, solve_schwarzschild (src/pprts.F90:2564-2566, 2630-2636)
+  TSX_EV_TOTAL
 };
 struct TsxLogPending { int ev; hipEvent_t a, b; };
 struct TsxLog {
-  long long count[TSX_EV_COUNT] = {0};
-  double ms[TSX_EV_COUNT] = {0};
+  long long count[TSX_EV_TOTAL] = {0};
+  double ms[TSX_EV_TOTAL] = {0};
   std::vector<TsxLogPending> pending;
   std::vector<hipEvent_t> pool;
 };

@@ -6,6 +6,7 @@
 //     E[s * Ncl + (k * ym + j) * xm + i],  k = 0..Nz (levels),  Ncl = (Nz+1) * ncol
 #pragma once
 #include "tsx_kernels.hpp"
+#include "tsx_kernels_1d.hpp"
 
 struct TsxSun {
   double phi, theta, mu, costheta, symmetry_phi;
@@ -582,25 +583,7 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_setup_b_solar(TsxGeo g, TsxSu
   }
 }
 
-// B_eff (src/schwarzschild.F90:36-67): 2-point Gauss-Legendre on (0,1)
-__device__ __forceinline__ double tsx_B_eff(double B_far, double B_near, double tau) {
-  const double pt[2] = {0.5 - 0.5 / 1.7320508075688772, 0.5 + 0.5 / 1.7320508075688772};
-  double B = 0.0;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const double mu = pt[q];
-    const double dtau = tau / mu;
-    double bmu;
-    if (dtau < 1e-3) {
-      bmu = (B_far + B_near) * .5;
-    } else {
-      const double tm1 = expm1(-dtau);
-      bmu = (-B_near + B_far * (tm1 + 1)) / (tm1) + ((B_far - B_near) * mu) / tau;
-    }
-    B += bmu * mu * 0.5;
-  }
-  return B * 2;
-}
+// B_eff (src/schwarzschild.F90:36-67) is tsx_B_eff, tsx_kernels_1d.hpp
 
 // Thermal: set_thermal_source (src/pprts.F90:4848-4987); planck at levels, reference layout (k over L fastest); bsrfc (xm, ym) = atm%Bsrfc or null
 template <int NTOP, int NSIDE, typename CT>
@@ -922,7 +905,7 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_eddington(TsxGeo g, const dou
                                                              double *__restrict__ a12, double *__restrict__ a13,
                                                              double *__restrict__ a23, double *__restrict__ a33) {
   const int xm = g.xm, ym = g.ym, Nz = g.Nz;
-  const double eps = 2.220446049250313e-16, tiny = 2.2250738585072014e-308;
+  const double tiny = 2.2250738585072014e-308;
   for (long long c = (long long)blockIdx.x * TSX_BLOCK + threadIdx.x; c < g.Nc; c += (long long)gridDim.x * TSX_BLOCK) {
     const int i = (int)(c % xm);
     const long long t_ = c / xm;
@@ -931,32 +914,8 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_eddington(TsxGeo g, const dou
     const size_t r = (size_t)k + (size_t)Nz * ((size_t)i + (size_t)xm * j);
     const double ext = fmax(tiny, kabs[r] + ksca[r]);
     const double dtau = dz[r] * ext, w0 = ksca[r] / ext, gg = gas[r];
-    const double f = 0.75 * gg;
-    const double g1 = 2.0 - w0 * (1.25 + f), g2 = w0 * (0.75 - f), g3 = 0.5 - mu0 * f;
-    const double slant = fmax(dtau / fmax(sqrt(tiny), mu0), 0.0);
     double tt, rr, rdir, sdir, tdir;
-    if (slant > 1e-6) {
-      const double g4 = 1.0 - g3;
-      const double al1 = g1 * g4 + g2 * g3, al2 = g1 * g3 + g2 * g4;
-      const double A = sqrt(fmax((g1 - g2) * (g1 + g2), 1e-12));
-      double kmu = A * mu0;
-      if (kmu <= 1.0 + 10.0 * eps && kmu >= 1.0 - 10.0 * eps) kmu = 1.0 - 10.0 * eps;  // approx(), helper_functions.fypp:1272
-      const double kg3 = A * g3, kg4 = A * g4;
-      const double e0 = exp(-slant), e = exp(-A * dtau), e2 = e * e, k2e = 2.0 * A * e;
-      double beta = 1.0 / (A + g1 + (A - g1) * e2);
-      rr = g2 * (1.0 - e2) * beta;
-      tt = k2e * beta;
-      beta = w0 * beta / (1.0 - kmu * kmu);
-      sdir = beta * (k2e * (g4 + al1 * mu0) - e0 * ((1.0 + kmu) * (al1 + kg4) - (1.0 - kmu) * (al1 - kg4) * e2));
-      rdir = beta * ((1.0 - kmu) * (al2 + kg3) - (1.0 + kmu) * (al2 - kg3) * e2 - k2e * (g3 - al2 * mu0) * e0);
-      tdir = e0;
-    } else {
-      tt = 1.0 - g1 * dtau;
-      rr = g2 * dtau;
-      sdir = (1.0 - g3) * (w0 * dtau);
-      rdir = g3 * (w0 * dtau);
-      tdir = 1.0 - slant;
-    }
+    tsx_eddington_ec(dtau, w0, gg, mu0, tt, rr, rdir, sdir, tdir);
     a11[c] = tt;
     a12[c] = rr;
     a13[c] = rdir;
@@ -971,14 +930,7 @@ __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_eddington(TsxGeo g, const dou
 // them are merged into solver layer 0 by `adding`, and solver layer k >= 1 is atmosphere layer atmk(k) = k + c - 1
 // (src/pprts_base.F90:1092).
 
-// schwarzschild_radiance (src/schwarzschild.F90:69-80)
-__device__ __forceinline__ double tsx_schwarzschild_radiance(double tau, double B_near, double B_far, double L) {
-  if (tau > 1e-3) {
-    const double tm1 = expm1(-tau);
-    return L * (tm1 + 1) + (B_far - B_near) - (B_near - (B_far - B_near) / tau) * tm1;
-  }
-  return (B_near + B_far) * .5 * tau + L * (1.0 - tau);
-}
+// schwarzschild_radiance (src/schwarzschild.F90:69-80) is tsx_schwarzschild_radiance, tsx_kernels_1d.hpp
 
 // adding (src/pprts.F90:2125-2198) over atmosphere layers 0 .. c-1 of one column per lane; handle_atm_collapse (:2080-2123) calls it
 // with a21 = a12, a22 = a11 (:2072-2073).  In: the atmosphere's cell-indexed Eddington planes a*a[k * ncol + col] (as tsx_k_eddington

@@ -412,6 +412,10 @@ extern "C" int tsx_pprts_set_optprop(tsx_solver *s, const double *kabs, const do
   ARGCHK(s && kabs && ksca && g && dz && albedo && l1d, "tsx_pprts_set_optprop: null argument");
   ARGCHK(dx > 0 && dy > 0, "tsx_pprts_set_optprop: dx, dy must be positive");
   if (int rc_c = tsx_refuse_collapsed(s, "tsx_pprts_set_optprop")) return rc_c;
+  if (s->mode_1d) {
+    tsx_set_error("tsx_pprts_set_optprop: a handle with a 1-D solver takes tsx_pprts_set_optical_properties");
+    return TSX_ERR_STATE;
+  }
   int rc = pipeline_guard(s, "tsx_pprts_set_optprop");
   if (rc) return rc;
   HIPCHK(hipSetDevice(s->device));
@@ -568,6 +572,58 @@ static int collapse_optprop(tsx_solver *s, const double *albedo, const double *k
   return TSX_OK;
 }
 
+// tsx_pprts_set_optical_properties on a handle with a 1-D solver (tsx_pprts_set_1d_solver): the fields of the atmosphere's
+// Nz + c - 1 layers, delta-scaled, and the surface terms -- "dont need LUT, we just compute Twostream anyway" (src/pprts.F90:536).
+// No 1-D detection, no coefficient lookups, no preconditioner set-up, and so no reduction over the ranks either.
+static int optprop_1d(tsx_solver *s, const double *albedo, const double *kabs, const double *ksca, const double *g, const double *dz,
+                      const double *planck, const double *planck_srfc, double dx, double dy, int ldelta_scaling, int where) {
+  const TsxGeo &gm = s->geo;
+  const int c = s->collapse > 1 ? s->collapse : 1, nz_atm = gm.Nz + c - 1;
+  const size_t ncol = (size_t)gm.ncol, nca = (size_t)nz_atm * ncol;
+  const hipMemcpyKind mk = where == TSX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  int rc;
+  TsxLogScope log_scope(s, TSX_EV_SET_OPTPROP);
+  double *pk = nullptr, *ps = nullptr, *pg = nullptr;
+  if (c > 1) {
+    TsxCollapseScratch A;
+    if ((rc = collapse_scratch(s, nz_atm, &A))) return rc;
+    if ((rc = keep_field(s, &A.kabs, kabs, nca, where))) return rc;
+    if ((rc = keep_field(s, &A.ksca, ksca, nca, where))) return rc;
+    if ((rc = keep_field(s, &A.g, g, nca, where))) return rc;
+    if ((rc = keep_field(s, &A.dz, dz, nca, where))) return rc;
+    if (planck && (rc = keep_field(s, &A.planck, planck, (size_t)(nz_atm + 1) * ncol, where))) return rc;
+    s->ca_have_B = planck != nullptr;  // (here: "the atmosphere's planck is held"; atm%Btop / Bbot are not needed by a 1-D solver)
+    pk = A.kabs, ps = A.ksca, pg = A.g;
+  } else {
+    if ((rc = keep_field(s, &s->d_kabs, kabs, nca, where))) return rc;
+    if ((rc = keep_field(s, &s->d_ksca, ksca, nca, where))) return rc;
+    if ((rc = keep_field(s, &s->d_g, g, nca, where))) return rc;
+    if ((rc = keep_field(s, &s->d_dz, dz, nca, where))) return rc;
+    if (planck) {
+      if ((rc = keep_field(s, &s->planck, planck, (size_t)(nz_atm + 1) * ncol, where))) return rc;
+    } else if (s->planck) {
+      HIPCHK(tsx_dev_free(s->planck));
+      s->planck = nullptr;
+    }
+    pk = s->d_kabs, ps = s->d_ksca, pg = s->d_g;
+  }
+  HIPCHK(hipMemcpyAsync(s->albedo, albedo, sizeof(double) * ncol, mk, s->stream));
+  s->have_albedo = true;
+  if (ldelta_scaling)
+    hipLaunchKernelGGL(tsx_k_delta_scale, dim3(grid_for((long long)nca)), dim3(TSX_BLOCK), 0, s->stream, (long long)nca, pk, ps, pg);
+  HIPCHK(hipGetLastError());
+  if ((rc = keep_planck_srfc(s, planck_srfc, where))) return rc;
+  HIPCHK(hipStreamSynchronize(s->stream));
+  s->have_coeffs = false;
+  s->pcx_valid = s->coef_h_valid = false;
+  s->opt_dx = dx;
+  s->opt_dy = dy;
+  s->have_optprop = true;
+  s->dir_coeffs_valid = false;
+  s->dir_seam = false;
+  return TSX_OK;
+}
+
 // set_optical_properties (src/pprts.F90:1764-2000) on the device: delta scaling (:1903-1917), which layers are 1-D
 // (:669-677), their Eddington coefficients (:1962-1992), then the coefficient lookups.  Raw (unscaled) fields in.
 extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *albedo, const double *kabs, const double *ksca,
@@ -577,6 +633,10 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
   ARGCHK(dx > 0 && dy > 0, "tsx_pprts_set_optical_properties: dx, dy must be positive");
   int rc = pipeline_guard(s, "tsx_pprts_set_optical_properties");
   if (rc) return rc;
+  if (s->mode_1d) {
+    HIPCHK(hipSetDevice(s->device));
+    return optprop_1d(s, albedo, kabs, ksca, g, dz, planck, planck_srfc, dx, dy, ldelta_scaling, where);
+  }
   if (!s->have_sun) {
     tsx_set_error("tsx_pprts_set_optical_properties: call tsx_pprts_set_angles first (Eddington coefficients need mu0)");
     return TSX_ERR_STATE;
@@ -683,6 +743,7 @@ static void slots_free(tsx_solver *s) {
   for (auto &kv : *m) {
     if (kv.second.x32) (void)tsx_dev_free(kv.second.x32);
     if (kv.second.e32) (void)tsx_dev_free(kv.second.e32);
+    if (kv.second.od) (void)tsx_dev_free(kv.second.od);
   }
   delete m;
   s->slots = nullptr;
@@ -694,6 +755,30 @@ extern "C" int tsx_pprts_select_solution(tsx_solver *s, int32_t uid) {
   if (!s->slots) s->slots = new std::map<int, TsxSolSlot>();
   auto &m = *(std::map<int, TsxSolSlot> *)s->slots;
   if (uid == s->cur_uid && m.count(uid)) return TSX_OK;
+  if (s->mode_1d) {  // 1-D solutions: W/m2 fluxes + absorption, parked as they are (nothing warm-starts from them)
+    const size_t nb = sizeof(double) * tsx_1d_solution_doubles(s);
+    if (s->have_solution && s->sol_is_1d) {
+      TsxSolSlot &cur = m[s->cur_uid];
+      if (!cur.od) HIPCHK(tsx_dev_malloc((void **)&cur.od, nb));
+      int rc = tsx_d2d(s, cur.od, s->od_flux, nb);
+      if (rc) return rc;
+      cur.lsolar = s->last_lsolar;
+    }
+    auto it1 = m.find(uid);
+    if (it1 != m.end() && it1->second.od) {
+      int rc = tsx_d2d(s, s->od_flux, it1->second.od, nb);
+      if (rc) return rc;
+      s->have_solution = s->sol_is_1d = true;
+      s->last_lsolar = it1->second.lsolar;
+    } else {
+      s->have_solution = s->sol_is_1d = false;
+    }
+    s->guess_foreign = false;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->cur_uid = uid;
+    if (!m.count(uid)) m[uid] = TsxSolSlot{nullptr, nullptr, 0};
+    return TSX_OK;
+  }
   const TsxGeo &g = s->geo;
   const long long ne = (long long)dir_streams(s) * (g.Nz + 1) * g.ncol;
   // park the working solution under the uid it belongs to
@@ -779,10 +864,69 @@ extern "C" int tsx_pprts_set_collapse(tsx_solver *s, int32_t collapseindex) {
   s->pcr_have_R = 0;
   slots_free(s);
   s->cur_uid = 0;
-  s->have_solution = s->guess_foreign = false;
+  s->have_solution = s->guess_foreign = s->sol_is_1d = false;
   s->its_hint_cold = s->its_hint_warm = 0;
   s->its_hint_key = 0;
   return tsx_pprts_zero_guess(s);
+}
+
+// t_solver_2str / -schwarzschild (src/pprts.F90:2627-2638): from the next tsx_pprts_set_optical_properties on, tsx_pprts_solve
+// answers with the 1-D column solver.  A changed mode is another solver: coefficients, optical properties, stored solutions and the
+// initial guess are dropped, as tsx_pprts_set_collapse drops them.  A changed nmu alone keeps them (it enters at the next solve).
+extern "C" int tsx_pprts_set_1d_solver(tsx_solver *s, int32_t mode, int32_t nmu) {
+  ARGCHK(s, "tsx_pprts_set_1d_solver: null");
+  ARGCHK(mode == TSX_1D_OFF || mode == TSX_1D_TWOSTREAM || mode == TSX_1D_SCHWARZSCHILD,
+         "tsx_pprts_set_1d_solver: mode must be TSX_1D_OFF, TSX_1D_TWOSTREAM or TSX_1D_SCHWARZSCHILD");
+  ARGCHK(nmu >= 1 && nmu <= 16, "tsx_pprts_set_1d_solver: nmu must be 1..16");
+  s->od_nmu = nmu;
+  if (mode == s->mode_1d) return TSX_OK;
+  HIPCHK(hipSetDevice(s->device));
+  s->mode_1d = mode;
+  s->have_optprop = s->have_coeffs = false;
+  s->dir_coeffs_valid = s->dir_seam = s->dir_seam_S = false;
+  s->pcx_valid = s->coef_h_valid = false;
+  s->ca_have_B = false;
+  s->dd_from_coords = false;
+  s->pcr_have_R = 0;
+  slots_free(s);
+  s->cur_uid = 0;
+  s->have_solution = s->guess_foreign = s->sol_is_1d = false;
+  s->its_hint_cold = s->its_hint_warm = 0;
+  s->its_hint_key = 0;
+  return tsx_pprts_zero_guess(s);
+}
+
+// -initial_guess_from_2str (src/pprts.F90:2560-2567): twostream on the optical properties the handle holds, scattered into the
+// solution storage in W per stream (tsx_1d.hip); the next tsx_pprts_solve starts from it, still as the first solve of its uid
+// (-ksp_complete_initial_run applies: the guess is made inside `.not. solution%lset`).
+extern "C" int tsx_pprts_guess_from_2str(tsx_solver *s, double edirTOA, int lsolar) {
+  ARGCHK(s, "tsx_pprts_guess_from_2str: null");
+  if (s->mode_1d) {
+    tsx_set_error("tsx_pprts_guess_from_2str: this handle solves with a 1-D solver, there is no 3-D solve to start");
+    return TSX_ERR_STATE;
+  }
+  if (!s->have_optprop) {
+    tsx_set_error("tsx_pprts_guess_from_2str: call tsx_pprts_set_optical_properties first");
+    return TSX_ERR_STATE;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  const TsxGeo &g = s->geo;
+  int rc;
+  {
+    TsxLogScope log_scope(s, TSX_EV_SOLVE_TWOSTREAM);
+    if ((rc = tsx_1d_run(s, edirTOA, lsolar, 0))) return rc;
+    if (lsolar && !s->edir_a)
+      HIPCHK(tsx_dev_malloc((void **)&s->edir_a, sizeof(double) * dir_streams(s) * (size_t)(g.Nz + 1) * g.ncol));
+    if ((rc = tsx_1d_scatter(s, lsolar, s->opt_dx, s->opt_dy, s->vx, s->edir_a))) return rc;
+  }
+  if ((rc = dir_halo_zero(s))) return rc;  // faces exchanged for an earlier beam do not belong to this guess
+  HIPCHK(hipStreamSynchronize(s->stream));
+  s->x_is_zero = false;
+  s->sol_is_1d = false;
+  s->have_solution = true;   // the working vectors hold a guess that is not this uid's solution: the solve that follows is the
+  s->guess_foreign = true;   // first of its uid, keeps the guess whatever its kind, and nothing parks it (src/pprts.F90:2532-2575)
+  s->last_lsolar = lsolar;
+  return TSX_OK;
 }
 
 __global__ __launch_bounds__(TSX_BLOCK) void tsx_k_asum(long long n, const double *__restrict__ v, double *__restrict__ partials) {
@@ -1012,6 +1156,33 @@ static int pprts_solve_t(tsx_solver *s, double edirTOA, int lsolar, const tsx_ks
 
 extern "C" int tsx_pprts_solve(tsx_solver *s, double edirTOA, int lsolar, const tsx_ksp_opts *opts, tsx_ksp_result *res) {
   ARGCHK(s, "tsx_pprts_solve: null");
+  if (s->mode_1d) {  // class is (t_solver_2str), src/pprts.F90:2627-2638
+    if (!s->have_optprop) {
+      tsx_set_error("tsx_pprts_solve: call tsx_pprts_set_optical_properties first");
+      return TSX_ERR_STATE;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    const int schwarz = s->mode_1d == TSX_1D_SCHWARZSCHILD && !lsolar;
+    hipEvent_t e0 = s->ev0, e1 = s->ev1;
+    HIPCHK(hipEventRecord(e0, s->stream));
+    {
+      TsxLogScope log_scope(s, schwarz ? TSX_EV_SOLVE_SCHWARZSCHILD : TSX_EV_SOLVE_TWOSTREAM);
+      int rc = tsx_1d_run(s, edirTOA, lsolar, schwarz);
+      if (rc) return rc;
+    }
+    HIPCHK(hipEventRecord(e1, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->last_lsolar = lsolar;
+    s->have_solution = s->sol_is_1d = true;
+    s->guess_foreign = false;
+    if (res) {
+      memset(res, 0, sizeof(*res));
+      res->reason = schwarz ? TSX_REASON_1D_SCHWARZSCHILD : TSX_REASON_1D_TWOSTREAM;
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) res->solve_ms = ms;
+    }
+    return TSX_OK;
+  }
   return PIPE_CALL(pprts_solve_t, s, edirTOA, lsolar, opts, res);
 }
 
@@ -1072,6 +1243,35 @@ static int pprts_get_result_t(tsx_solver *s, double *edn, double *eup, double *a
 
 extern "C" int tsx_pprts_get_result(tsx_solver *s, double *edn, double *eup, double *abso, double *edir, int where) {
   ARGCHK(s && edn && eup && abso, "tsx_pprts_get_result: null argument");
+  if (s->have_solution && s->sol_is_1d) {
+    // a 1-D solution is lWm2 = .true. and lchanged = .false. (src/pprts_1D_solvers.F90:241-245): restore_solution neither scales
+    // it nor computes a flux divergence; pprts_get_result's `* sun%mu` (src/pprts.F90:5883-5888) applies
+    HIPCHK(hipSetDevice(s->device));
+    const TsxGeo &g = s->geo;
+    const size_t nl = (size_t)(g.Nz + 1) * g.ncol, nc = (size_t)g.Nc;
+    double *d_dn = edn, *d_up = eup, *d_ab = abso, *d_di = edir;
+    TsxDevTmp tmp_guard;
+    if (where == TSX_HOST) {
+      HIPCHK(tmp_guard.alloc(sizeof(double) * (3 * nl + nc)));
+      double *tmp = tmp_guard.as<double>();
+      d_dn = tmp, d_up = tmp + nl, d_di = edir ? tmp + 2 * nl : nullptr, d_ab = tmp + 3 * nl;
+    }
+    TsxLogScope log_res(s, TSX_EV_GET_RESULT);
+    int rc = tsx_1d_result(s, s->last_lsolar, d_dn, d_up, d_ab, d_di);
+    if (rc) return rc;
+    if (where == TSX_HOST) {
+      HIPCHK(hipMemcpyAsync(edn, d_dn, sizeof(double) * nl, hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipMemcpyAsync(eup, d_up, sizeof(double) * nl, hipMemcpyDeviceToHost, s->stream));
+      if (edir) HIPCHK(hipMemcpyAsync(edir, d_di, sizeof(double) * nl, hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipMemcpyAsync(abso, d_ab, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return TSX_OK;
+  }
+  if (s->mode_1d && !s->have_solution) {
+    tsx_set_error("tsx_pprts_get_result: no solution (call tsx_pprts_solve)");
+    return TSX_ERR_STATE;
+  }
   return PIPE_CALL(pprts_get_result_t, s, edn, eup, abso, edir, where);
 }
 
@@ -1123,7 +1323,7 @@ extern "C" int tsx_pprts_get_field(tsx_solver *s, int which, double *out, int wh
   if (which >= 13) {  // atm%Btop / atm%Bbot of a collapsed atmosphere (src/pprts.F90:2192-2196), (xs:xe, ys:ye); NaN without them
     HIPCHK(hipSetDevice(s->device));
     const size_t nb = sizeof(double) * (size_t)s->geo.ncol;
-    if (s->collapse > 1 && s->ca_have_B && s->have_optprop) {
+    if (s->collapse > 1 && s->ca_have_B && s->have_optprop && !s->mode_1d) {
       HIPCHK(hipMemcpyAsync(out, s->ca_B + (which == 14 ? s->geo.ncol : 0), nb,
                             where == TSX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
     } else if (where == TSX_HOST) {
@@ -1170,6 +1370,10 @@ extern "C" int tsx_pprts_get_field(tsx_solver *s, int which, double *out, int wh
   }
   int rc = pipeline_guard(s, "tsx_pprts_get_field");
   if (rc) return rc;
+  if (s->mode_1d) {  // a 1-D solution has no stream vectors, no source vector and no direct coefficients
+    tsx_set_error("tsx_pprts_get_field: fields 0..4 do not exist on a handle with a 1-D solver (tsx_pprts_set_1d_solver)");
+    return TSX_ERR_STATE;
+  }
   HIPCHK(hipSetDevice(s->device));
   const TsxGeo &g = s->geo;
   size_t n = 0;

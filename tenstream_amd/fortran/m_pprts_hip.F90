@@ -23,6 +23,7 @@ module m_pprts_hip
     & tsx_lut_set_diffuse, tsx_lut_load_diffuse_mmap4, tsx_lut_set_direct, tsx_lut_load_direct_mmap4, &
     & tsx_diff_set_optprop, tsx_diff_get_coeffs, &
     & tsx_pprts_set_angles, tsx_pprts_set_collapse, tsx_pprts_set_direct_tolerances, tsx_pprts_set_optical_properties, tsx_pprts_set_optprop, &
+    & tsx_pprts_set_1d_solver, tsx_pprts_guess_from_2str, TSX_1D_OFF, TSX_1D_TWOSTREAM, TSX_1D_SCHWARZSCHILD, &
     & tsx_pprts_solve, tsx_pprts_zero_guess, tsx_pprts_select_solution, tsx_pprts_get_result, tsx_pprts_get_field, &
     & TSX_HOST, TSX_DEVICE, TSX_PC_NONE, TSX_PC_COLUMN, TSX_PC_ZEBRA, TSX_PC_REDBLACK
 
@@ -58,6 +59,7 @@ module m_pprts_hip
 
   integer(c_int), parameter :: TSX_HOST = 0, TSX_DEVICE = 1
   integer(c_int), parameter :: TSX_PC_NONE = 0, TSX_PC_COLUMN = 1, TSX_PC_ZEBRA = 2, TSX_PC_REDBLACK = 3
+  integer(c_int32_t), parameter :: TSX_1D_OFF = 0, TSX_1D_TWOSTREAM = 1, TSX_1D_SCHWARZSCHILD = 2
 
   ! mirrors tsx_grid (include/tsx.h) == the fields of t_coord the back-end needs (src/pprts_base.F90:92-109)
   type, bind(C) :: t_tsx_grid
@@ -304,6 +306,21 @@ module m_pprts_hip
       import :: c_ptr, c_int, c_int32_t
       type(c_ptr), value :: handle
       integer(c_int32_t), value :: collapseindex
+      integer(c_int) :: ierr
+    end function
+    !> t_solver_2str / -schwarzschild (src/pprts.F90:2627-2638): mode = TSX_1D_OFF / TSX_1D_TWOSTREAM / TSX_1D_SCHWARZSCHILD, nmu 1..16
+    function tsx_pprts_set_1d_solver(handle, mode, nmu) bind(C, name='tsx_pprts_set_1d_solver') result(ierr)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: mode, nmu
+      integer(c_int) :: ierr
+    end function
+    !> -initial_guess_from_2str (src/pprts.F90:2560-2567) as a call: the next tsx_pprts_solve starts from the two-stream fluxes
+    function tsx_pprts_guess_from_2str(handle, edirTOA, lsolar) bind(C, name='tsx_pprts_guess_from_2str') result(ierr)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: handle
+      real(c_double), value :: edirTOA
+      integer(c_int), value :: lsolar
       integer(c_int) :: ierr
     end function
     function tsx_pprts_set_direct_tolerances(handle, rtol, atol, maxit) bind(C, name='tsx_pprts_set_direct_tolerances') result(ierr)

@@ -100,12 +100,15 @@ def adding(a11, a12, a13, a23, a33, dtau=None, planck=None):
 class PprtsSolver:
     """One pprts solver (3_10) on one GPU, driven like the reference's Fortran/C API."""
 
-    def __init__(self, Nz, Nx, Ny, dx, dy, phi0, theta0, solver="3_10", device=-1, collapseindex=1, **decomposition):
+    def __init__(self, Nz, Nx, Ny, dx, dy, phi0, theta0, solver="3_10", device=-1, collapseindex=1, solver_1d=None, nmu=2,
+                 **decomposition):
         """Nx, Ny: the columns this rank owns; decomposition: xs, ys, glob_xm, glob_ym, rank, nranks, neighbors (W, E, S, N)
         as DiffuseSolver takes them (several ranks: call core.comm_init / core.comm_set_callbacks before the first
         set_optical_properties), force_halo for tests.  collapseindex as init_pprts takes it (src/pprts.F90:213, 1067-1078):
         Nz is the atmosphere's layer count, and with collapseindex = c > 1 the top c layers are merged into one, so that the
-        solver (self.Nz, the results) has Nz - c + 1 layers (tsx_pprts_set_collapse)."""
+        solver (self.Nz, the results) has Nz - c + 1 layers (tsx_pprts_set_collapse).  solver_1d = "twostream" | "schwarzschild":
+        the handle answers every solve with the 1-D column solver (t_solver_2str, -schwarzschild with nmu nodes;
+        src/pprts.F90:2627-2638, tsx_pprts_set_1d_solver) and needs no look-up tables."""
         c = max(int(collapseindex), 1)
         self.Nz_atm, self.collapse = int(Nz), c
         self.Nz, self.Nx, self.Ny, self.dx, self.dy = int(Nz) - c + 1, int(Nx), int(Ny), float(dx), float(dy)
@@ -119,6 +122,25 @@ class PprtsSolver:
         self.mu0 = max(np.cos(np.deg2rad(theta0)), 0.0) if theta0 < 90 else 0.0
         if c > 1:
             _lib.check(self.lib.tsx_pprts_set_collapse(self.h, c))
+        self.solver_1d = None
+        if solver_1d is not None:
+            self.set_1d_solver(solver_1d, nmu)
+
+    MODES_1D = {None: 0, "off": 0, "twostream": 1, "schwarzschild": 2}
+
+    def set_1d_solver(self, solver_1d, nmu=2):
+        """tsx_pprts_set_1d_solver: None | "twostream" | "schwarzschild".  A changed mode drops the optical properties, the
+        coefficients and the stored solutions."""
+        if solver_1d not in self.MODES_1D:
+            raise ValueError(f"solver_1d must be one of {sorted(k for k in self.MODES_1D if k)} or None, not {solver_1d!r}")
+        _lib.check(self.lib.tsx_pprts_set_1d_solver(self.h, self.MODES_1D[solver_1d], int(nmu)))
+        self.solver_1d = solver_1d if self.MODES_1D[solver_1d] else None
+
+    def guess_from_2str(self, edirTOA, lsolar=None):
+        """-initial_guess_from_2str (src/pprts.F90:2560-2567): the next solve starts from the two-stream fluxes of the optical
+        properties set last (tsx_pprts_guess_from_2str)."""
+        lsolar = (edirTOA > 0) if lsolar is None else lsolar
+        _lib.check(self.lib.tsx_pprts_guess_from_2str(self.h, float(edirTOA), int(bool(lsolar))))
 
     def set_collapse(self, collapseindex):
         """tsx_pprts_set_collapse on this handle: the solver keeps its self.Nz layers, the next set_optical_properties takes
@@ -236,6 +258,10 @@ class PprtsSolver:
         _lib.check(self.lib.tsx_pprts_solve(self.h, float(edirTOA), int(bool(lsolar)), None if o is None else C.byref(o),
                                             C.byref(r)))
         return KspInfo(r.reason, r.niter, r.rnorm0, r.rnorm, np.array(r.res_hist[: r.nhist]), r.solve_ms, 0.0, 0.0)
+
+    def solve_select(self, uid):
+        """tsx_pprts_select_solution on its own: what solve(uid=...) does first, for a guess_from_2str in between"""
+        _lib.check(self.lib.tsx_pprts_select_solution(self.h, int(uid)))
 
     # -- pprts_get_result -----------------------------------------------------------------------------------
     def get_result(self, out=None):
