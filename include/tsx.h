@@ -374,6 +374,36 @@ int tsx_pprts_select_solution(tsx_solver *s, int32_t uid);
 /* restore_solution + pprts_get_result: edn, eup, edir (zs:ze, xs:xe, ys:ye), abso (zs:ze-1, xs:xe, ys:ye), W/m2 and
  * W/m3, solar results multiplied by sun%mu (src/pprts.F90:5883-5888).  edir may be NULL. */
 int tsx_pprts_get_result(tsx_solver *s, double *edn, double *eup, double *abso, double *edir, int where);
+/* ---- buildings: opt_buildings of solve_pprts / pprts_get_result (src/pprts.F90:2487, 5799; t_pprts_buildings,
+ *      src/buildings.F90:39-74).  A building is a list of cell faces, each opaque to the direct beam, reflecting diffusely with its
+ *      own albedo and, in the thermal, emitting with its own Planck value:
+ *        dir2dir   the whole block of a cell that owns a listed face is zero                               (src/pprts.F90:3194-3212)
+ *        diff2diff per face every coefficient into the dofs that leave the cell through it is zero, the ones from the dofs entering
+ *                  through the same face are albedo / streams (stored as real32 like the blocks)           (:3579-3677)
+ *        setup_b   the source of the face's leaving dofs is overwritten: solar 0 + sum of the face's direct dofs * albedo / streams;
+ *                  thermal, with planck, A_face * pi * planck * (1 - albedo) / streams                      (:4669-4672, 4989-5145)
+ *      iface[m]: the reference's 1-based linear index over [face_id, k, i, j] with sizes [6, Nz, xm, ym], first dimension fastest
+ *      (faceidx_by_cell_plus_offset, src/buildings.F90:217-222; ind_1d_to_nd, src/helper_functions.fypp:2392-2414); face ids 1..6 =
+ *      TOP, BOT, LEFT, RIGHT, REAR, FRONT (src/boxmc_geometry.F90:46-51).  albedo[m] in [0, 1]; planck[m] or NULL.  nfaces = 0 detaches.
+ *      Call it BEFORE tsx_pprts_set_optical_properties: the buildings take effect with the next coefficient set; a g-point loop calls
+ *      it per band with new albedos and the same faces (clone_buildings in the reference) -- only a changed face list is decoded
+ *      again.  Called after the optical properties were set it invalidates them: tsx_pprts_solve returns TSX_ERR_STATE until they are
+ *      set again.  Validated on the host: index (face id and cell) in range, no face twice, albedo in [0, 1]; a violation returns
+ *      TSX_ERR_ARG and names the first offending entry.  TSX_ERR_UNSUPPORTED: handles with more than one rank, collapsed handles
+ *      (tsx_pprts_set_collapse), 1-D-solver handles (tsx_pprts_set_1d_solver) -- here or, if those were switched on later, in
+ *      tsx_pprts_set_optical_properties, which also refuses a face in a layer that is solved 1-D (there the reference ignores the patched
+ *      block but still overwrites the source), and tsx_pprts_set_optprop while buildings are attached.
+ *      The seam entries (tsx_diff_set_coeffs, tsx_diff_set_optprop, tsx_dir_set_coeffs, tsx_dir_solve, tsx_setup_b_solar / _thermal,
+ *      tsx_diff_solve) IGNORE attached buildings: their caller owns the coefficients and the source and patches them itself. */
+int tsx_pprts_set_buildings(tsx_solver *s, int64_t nfaces, const int64_t *iface, const double *albedo, const double *planck_or_NULL,
+                            int where);
+/* fill_buildings_arr (src/pprts.F90:6011-6247, without -pprts_fill_1D_side_walls): per face, in the order of iface, the direct,
+ * incoming diffuse and outgoing diffuse irradiance in W/m2, solar ones multiplied by sun%mu.  After a solve, valid under the same
+ * conditions as tsx_pprts_get_result; without a solar solve edir is filled with zeros.  edir may be NULL. */
+int tsx_pprts_get_buildings(tsx_solver *s, double *edir_or_NULL, double *incoming, double *outgoing, int where);
+/* -pprts_set_abso_in_buildings <val> (src/pprts.F90:5986-6009): on != 0: tsx_pprts_get_result returns val as the absorption of every
+ * cell that owns a building face */
+int tsx_pprts_set_abso_in_buildings(tsx_solver *s, int on, double val);
 /* parity probes: which = 0 edir [W] (0:S-1, zs:ze, xs:xe, ys:ye); 1 b [W]; 2 ediff [W] (0:D-1, zs:ze, ...);
  * 3 dir2dir (S*S, zs:ze-1, ...); 4 dir2diff (S*D, ...) -- reference layouts, real64;
  * what tsx_pprts_set_optical_properties derived on the device, (zs:ze-1, xs:xe, ys:ye): 5 kabs, 6 ksca, 7 g after delta scaling

@@ -59,6 +59,7 @@ SYMBOLS = (
     "tsx_probe_bandwidth", "tsx_diff_apply_r", "tsx_diff_solve_r", "tsx_dir_set_coeffs", "tsx_dir_solve", "tsx_setup_b_solar", "tsx_setup_b_thermal",
     "tsx_debug_code_read", "tsx_log_enable", "tsx_log_get", "tsx_pool_stats", "tsx_pool_check",
     "tsx_pool_debug_overrun", "tsx_pprts_set_collapse", "tsx_pprts_set_1d_solver", "tsx_pprts_guess_from_2str",
+    "tsx_pprts_set_buildings", "tsx_pprts_get_buildings", "tsx_pprts_set_abso_in_buildings",
 )
 
 PEER_BLOB_BYTES = 192   # TSX_PEER_BLOB_BYTES
@@ -103,6 +104,9 @@ def load():
     lib.tsx_pprts_set_collapse.argtypes = [vp, C.c_int32]
     lib.tsx_pprts_set_1d_solver.argtypes = [vp, C.c_int32, C.c_int32]
     lib.tsx_pprts_guess_from_2str.argtypes = [vp, C.c_double, C.c_int]
+    lib.tsx_pprts_set_buildings.argtypes = [vp, C.c_int64, vp, vp, vp, ip]
+    lib.tsx_pprts_get_buildings.argtypes = [vp, vp, vp, vp, ip]
+    lib.tsx_pprts_set_abso_in_buildings.argtypes = [vp, ip, C.c_double]
     lib.tsx_lut_set_direct.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, vp, ip]
     lib.tsx_lut_load_direct_mmap4.argtypes = [vp, C.c_char_p, C.c_char_p]
     lib.tsx_pprts_set_optprop.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip]

@@ -310,6 +310,7 @@ extern "C" int tsx_destroy(tsx_solver *s) {
     if (s->host_recv[q]) (void)hipHostFree(s->host_recv[q]);
   }
   slots_free(s);
+  tsx_buildings_free(s);
   tsx_log_free(s);
   delete s->flow_pr_shadow;
   if (s->comm_ready && g_rccl.CommDestroy) {
@@ -728,7 +729,12 @@ int tsx_cell_samples(tsx_solver *s, const double *kabs, const double *ksca, cons
 }
 
 // alloc_coeff_diff2diff on the device: kabs/ksca/g/dz are device pointers in the reference layout
-static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx) {
+// buildings (tsx_pprts_set_optical_properties with buildings attached only; the seam entries ignore them): the blocks are patched
+// in the dense planes BEFORE anything is shared, so the coordinate-keyed sharing -- which never writes dense planes and whose
+// "previous grouping still exact" reuse (TSX_DEDUP_REUSE) looks at coordinates alone -- is skipped, and the block-based build
+// (tsx_dedup_ensure) groups the patched blocks by their renewed hashes and an exact compare
+static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx,
+                              bool buildings = false) {
   TsxLogScope log_scope(s, TSX_EV_GET_COEFF_DIFF2DIFF);  // get_coeff_diff2diff, src/pprts.F90:3422-3489
   const TsxGeo &gm = s->geo;
   // a new coefficient set: whatever the shared storage held is gone (the callers used to reset these after the launch; the
@@ -737,6 +743,7 @@ static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *k
   s->dd_on = false;
   s->dd_pc = false;
   s->coef_dense_valid = true;
+  s->dd_blocks_patched = false;
   TsxLutDev L;
   memset(&L, 0, sizeof(L));
   const TsxLutHost &H = s->lut_diff;
@@ -757,11 +764,13 @@ static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *k
   if (rcs) return rcs;
   // sharing keyed on the cells' LUT coordinates, before anything is interpolated (tsx_dedup.hip "coordinates first"): where
   // it pays only the distinct tuples are interpolated, straight into the shared storage, and no dense planes are written
-  {
+  if (!buildings) {
     bool built = false;
     int rc = tsx_dedup_from_coords(s, L, &built);
     if (rc) return rc;
     if (built) return TSX_OK;
+  } else {
+    s->dd_from_coords = false;  // no grouping by coordinates is current, none is taken over by the next set
   }
   unsigned long long *hash = nullptr;  // the kernel leaves the blocks' hashes for the shared storage (tsx_dedup.hip)
   {
@@ -777,6 +786,11 @@ static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *k
     hipLaunchKernelGGL((tsx_k_lut_diff2diff<256>), dim3(nbk), dim3(TSX_BLOCK), 0, s->stream, gm, L, kabs, ksca, g, dz, dx,
                        s->l1d, (float *)s->coef, hash, samp);
   s->dd_hash_ready = hash != nullptr;
+  if (buildings) {
+    int rc = tsx_buildings_patch_diffuse(s, hash);
+    if (rc) return rc;
+    s->dd_blocks_patched = true;
+  }
   return TSX_OK;
 }
 

@@ -387,7 +387,8 @@ static int dd_build(tsx_solver *s, bool near, bool *pays) {
   else if (!s->dd_hash_ready)  // else tsx_k_lut_diff2diff has left the hashes of the blocks it produced (tsx_dedup_hash_buffer)
     hipLaunchKernelGGL(tsx_k_dd_hash, dim3(nb), dim3(TSX_BLOCK), 0, s->stream, g, DD, C, s->l1d, th.as<unsigned long long>());
   // the blocks came from tsx_k_lut_diff2diff a moment ago: the cells' LUT coordinates are still there (tsx_cell_samples)
-  const float4 *samp = (!near && s->dd_hash_ready) ? (const float4 *)s->cell_samp : (const float4 *)nullptr;
+  // (not where buildings patched some blocks after the lookup: there every candidate pair is compared block by block)
+  const float4 *samp = (!near && s->dd_hash_ready && !s->dd_blocks_patched) ? (const float4 *)s->cell_samp : (const float4 *)nullptr;
   s->dd_hash_ready = false;
   hipLaunchKernelGGL(tsx_k_dd_insert, dim3(nb), dim3(TSX_BLOCK), 0, s->stream, Nc, tsz - 1, th.as<unsigned long long>(),
                      tk.as<unsigned long long>(), to.as<int>());

@@ -200,3 +200,11 @@ int tsx_1d_scatter(tsx_solver *s, int lsolar, double dx, double dy, double *x, d
 size_t tsx_1d_solution_doubles(const tsx_solver *s);
 void tsx_gauss_legendre_01(int n, double *mu, double *w);
 int tsx_dedup_hash_buffer(tsx_solver *s, unsigned long long **h);
+// buildings (tsx_buildings.hip); every caller gates on s->bld_nfaces > 0 on the host: a handle without buildings launches nothing
+int tsx_buildings_refuse(const tsx_solver *s, const char *who);                 // TSX_ERR_UNSUPPORTED on several ranks, with collapse, with a 1-D solver
+int tsx_buildings_check_layers(const tsx_solver *s, const uint8_t *l1d_host);   // ... and for a face in a 1-D layer
+int tsx_buildings_patch_diffuse(tsx_solver *s, unsigned long long *hash);       // dense diff2diff planes + the patched cells' hashes
+int tsx_buildings_zero_dir(tsx_solver *s);                                      // dir2dir planes
+int tsx_buildings_source(tsx_solver *s, int lsolar);                            // s->vb behind setup_b
+int tsx_buildings_abso(tsx_solver *s, double *abso_dev);                        // -pprts_set_abso_in_buildings on a result array
+void tsx_buildings_free(tsx_solver *s);

@@ -73,6 +73,7 @@ struct TsxSolSlot {  // one stored solution (initial guess of the next solve wit
 };
 
 struct TsxPeer;  // tsx_peer.hip
+struct TsxBuildings;  // tsx_buildings.hip
 struct TsxLog;   // below: log events / roctx ranges
 
 // peer transport (tsx_peer_dev.hpp): what a kernel needs to consume a face message in place -- the sequence number that
@@ -188,6 +189,7 @@ struct tsx_solver {
   void *dd_scratch;        // work space of the build (hashes, table, scan)
   bool x_is_zero = false;      // the initial guess in vx is known to be zero on every rank (krylov_begin then skips A x0)
   bool dd_hash_ready = false;  // the hashes of the current blocks already sit in dd_scratch (left by tsx_k_lut_diff2diff)
+  bool dd_blocks_patched = false;  // ... but some blocks were patched after the lookup (buildings): equal LUT coordinates no longer mean equal blocks
   size_t dd_scratch_bytes;
   int n1d;             // number of 1-D layers (unconstrained_fraction = 1 - n1d/Nz, src/pprts.F90:721-723; with collapse: of the
                        // atmosphere's Nz + collapse - 1 layers, tsx_unconstrained_fraction)
@@ -287,7 +289,12 @@ struct tsx_solver {
   double *od_flux = nullptr;  // the 1-D solution: S, Edn, Eup [(Nz + c) * ncol] in W/m2, abso [Nz * ncol] in W/m3 (grow-only)
   size_t od_flux_cap = 0;
   bool sol_is_1d = false;     // the current solution is od_flux (lWm2 = .true., lchanged = .false.), not vx / edir_a
-  TsxLog *log = nullptr;     // the reference's log events for this path + roctx ranges (tsx_log_enable; off: null)
+  // buildings (opt_buildings of solve_pprts / pprts_get_result, src/buildings.F90:39-74; tsx_buildings.hip, tsx_pprts_set_buildings)
+  TsxBuildings *bld = nullptr;  // host copy of the face list + the device records (pool, grow-only); null: never attached
+  int bld_nfaces = 0;           // > 0: buildings are attached -- the one thing the other units gate on
+  bool bld_abso_on = false;     // -pprts_set_abso_in_buildings <val> (src/pprts.F90:5986-6009)
+  double bld_abso_val = 0.0;
+  TsxLog *log = nullptr;    // the reference's log events for this path + roctx ranges (tsx_log_enable; off: null)
 };
 
 // atm%unconstrained_fraction (src/pprts.F90:721-723): the share of the ATMOSPHERE's layers that are not 1-D

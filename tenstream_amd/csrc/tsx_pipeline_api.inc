@@ -416,6 +416,11 @@ extern "C" int tsx_pprts_set_optprop(tsx_solver *s, const double *kabs, const do
     tsx_set_error("tsx_pprts_set_optprop: a handle with a 1-D solver takes tsx_pprts_set_optical_properties");
     return TSX_ERR_STATE;
   }
+  if (s->bld_nfaces > 0) {  // the blocks are patched inside tsx_pprts_set_optical_properties only
+    tsx_set_error("tsx_pprts_set_optprop: not available with buildings attached (tsx_pprts_set_buildings); use "
+                  "tsx_pprts_set_optical_properties");
+    return TSX_ERR_UNSUPPORTED;
+  }
   int rc = pipeline_guard(s, "tsx_pprts_set_optprop");
   if (rc) return rc;
   HIPCHK(hipSetDevice(s->device));
@@ -633,6 +638,7 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
   ARGCHK(dx > 0 && dy > 0, "tsx_pprts_set_optical_properties: dx, dy must be positive");
   int rc = pipeline_guard(s, "tsx_pprts_set_optical_properties");
   if (rc) return rc;
+  if (s->bld_nfaces > 0 && (rc = tsx_buildings_refuse(s, "tsx_pprts_set_optical_properties"))) return rc;
   if (s->mode_1d) {
     HIPCHK(hipSetDevice(s->device));
     return optprop_1d(s, albedo, kabs, ksca, g, dz, planck, planck_srfc, dx, dy, ldelta_scaling, where);
@@ -694,6 +700,10 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
   s->any_l1d = s->n1d > 0;
   HIPCHK(hipMemcpyAsync(s->l1d, l1d.data(), gm.Nz, hipMemcpyHostToDevice, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));  // l1d (stack) must outlive the copy
+  if (s->bld_nfaces > 0 && (rc = tsx_buildings_check_layers(s, l1d.data()))) {
+    s->have_optprop = s->have_coeffs = false;  // the fields above are already the new ones
+    return rc;
+  }
   if (s->any_l1d) {
     double **fields[5] = {&s->a11, &s->a12, &s->a13, &s->a23, &s->a33};
     for (double **f : fields)
@@ -703,7 +713,8 @@ extern "C" int tsx_pprts_set_optical_properties(tsx_solver *s, const double *alb
   }
   }
   if ((rc = ensure_coef_storage(s, 4))) return rc;
-  if ((rc = lut_diffuse_launch(s, s->d_kabs, s->d_ksca, s->d_g, s->d_dz, dx))) return rc;
+  // buildings: set_buildings_coeff of alloc_coeff_diff2diff (src/pprts.F90:3579-3677) behind the lookup, before the blocks are shared
+  if ((rc = lut_diffuse_launch(s, s->d_kabs, s->d_ksca, s->d_g, s->d_dz, dx, s->bld_nfaces > 0))) return rc;
   HIPCHK(hipGetLastError());
   if (planck) {
     if (s->collapse <= 1 && (rc = keep_field(s, &s->planck, planck, (size_t)(gm.Nz + 1) * gm.ncol, where))) return rc;
@@ -968,6 +979,8 @@ static int direct_solve(tsx_solver *s, double edirTOA, bool first_of_uid, bool s
                        s->d_ksca, s->d_g, s->d_dz, s->opt_dx, (float)sun.symmetry_phi, (float)sun.theta, sun.xinc == 0,
                        sun.yinc == 0, s->l1d, s->dirS, samp);
     HIPCHK(hipGetLastError());
+    // buildings: set_buildings_coeff of alloc_coeff_dir2dir (src/pprts.F90:3194-3212), behind the lookup (and its quadrant relabelling)
+    if (s->bld_nfaces > 0 && (rc = tsx_buildings_zero_dir(s))) return rc;
     s->dir_coeffs_valid = true;
   }
   if (!s->edir_a) {
@@ -1121,6 +1134,8 @@ static int pprts_solve_t(tsx_solver *s, double edirTOA, int lsolar, const tsx_ks
                          s->opt_dy, s->vb, (const double *)nullptr, (const int *)nullptr, 0ll, cB);
   }
   HIPCHK(hipGetLastError());
+  // buildings: set_buildings_reflection / set_buildings_emission overwrite the faces' leaving dofs (src/pprts.F90:4669-4672)
+  if (s->bld_nfaces > 0 && (rc = tsx_buildings_source(s, lsolar))) return rc;
   }
   s->last_lsolar = lsolar;
   // b_norm = sum |b| < atol -> skip the diffuse solve, ediff = b (src/pprts.F90:2773-2784)
@@ -1231,6 +1246,9 @@ static int pprts_get_result_t(tsx_solver *s, double *edn, double *eup, double *a
   hipLaunchKernelGGL((tsx_k_get_result<NTOP, NSIDE, DTOP, DSIDE>), dim3((g.ncol + 31) / 32, (g.Nz + 1 + 31) / 32), dim3(TSX_BLOCK), 0, s->stream, g, sun,
                      lsolar, s->opt_dx, s->opt_dy, dir_top_div(s), s->edir_a, s->vx, d_di, d_dn, d_up, d_ab);
   HIPCHK(hipGetLastError());
+  // -pprts_set_abso_in_buildings (src/pprts.F90:5986-6009).  The reference overwrites solution%abso behind the copy into rabso
+  // (:5881, 5909), so there the value shows in the dump and from the next pprts_get_result on; here it is in the array returned
+  if (s->bld_nfaces > 0 && s->bld_abso_on && (rc = tsx_buildings_abso(s, d_ab))) return rc;
   if (where == TSX_HOST) {
     HIPCHK(hipMemcpyAsync(edn, d_dn, sizeof(double) * nl, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipMemcpyAsync(eup, d_up, sizeof(double) * nl, hipMemcpyDeviceToHost, s->stream));

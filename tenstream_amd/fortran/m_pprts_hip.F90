@@ -24,6 +24,7 @@ module m_pprts_hip
     & tsx_diff_set_optprop, tsx_diff_get_coeffs, &
     & tsx_pprts_set_angles, tsx_pprts_set_collapse, tsx_pprts_set_direct_tolerances, tsx_pprts_set_optical_properties, tsx_pprts_set_optprop, &
     & tsx_pprts_set_1d_solver, tsx_pprts_guess_from_2str, TSX_1D_OFF, TSX_1D_TWOSTREAM, TSX_1D_SCHWARZSCHILD, &
+    & tsx_pprts_set_buildings, tsx_pprts_get_buildings, tsx_pprts_set_abso_in_buildings, &
     & tsx_pprts_solve, tsx_pprts_zero_guess, tsx_pprts_select_solution, tsx_pprts_get_result, tsx_pprts_get_field, &
     & TSX_HOST, TSX_DEVICE, TSX_PC_NONE, TSX_PC_COLUMN, TSX_PC_ZEBRA, TSX_PC_REDBLACK
 
@@ -321,6 +322,31 @@ module m_pprts_hip
       type(c_ptr), value :: handle
       real(c_double), value :: edirTOA
       integer(c_int), value :: lsolar
+      integer(c_int) :: ierr
+    end function
+    !> opt_buildings of solve_pprts / pprts_get_result (src/pprts.F90:2487, 5799; t_pprts_buildings, src/buildings.F90:39-74):
+    !> iface = c_loc of B%iface as integer(c_int64_t) (the reference's linear indices unchanged), albedo = c_loc(B%albedo), planck =
+    !> c_loc(B%planck) or c_null_ptr, real64; before tsx_pprts_set_optical_properties; nfaces = 0 detaches (include/tsx.h)
+    function tsx_pprts_set_buildings(handle, nfaces, iface, albedo, planck, where) bind(C, name='tsx_pprts_set_buildings') result(ierr)
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: handle, iface, albedo, planck
+      integer(c_int64_t), value :: nfaces
+      integer(c_int), value :: where
+      integer(c_int) :: ierr
+    end function
+    !> fill_buildings_arr (src/pprts.F90:6011-6247): B%edir (or c_null_ptr), B%incoming, B%outgoing per face in W/m2, after a solve
+    function tsx_pprts_get_buildings(handle, edir, incoming, outgoing, where) bind(C, name='tsx_pprts_get_buildings') result(ierr)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: handle, edir, incoming, outgoing
+      integer(c_int), value :: where
+      integer(c_int) :: ierr
+    end function
+    !> -pprts_set_abso_in_buildings <val> (src/pprts.F90:5986-6009), applied by tsx_pprts_get_result
+    function tsx_pprts_set_abso_in_buildings(handle, on, val) bind(C, name='tsx_pprts_set_abso_in_buildings') result(ierr)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: on
+      real(c_double), value :: val
       integer(c_int) :: ierr
     end function
     function tsx_pprts_set_direct_tolerances(handle, rtol, atol, maxit) bind(C, name='tsx_pprts_set_direct_tolerances') result(ierr)

@@ -97,6 +97,21 @@ def adding(a11, a12, a13, a23, a33, dtau=None, planck=None):
     return merged, (eup * 2 * np.pi / np.pi, edn * 2 * np.pi / np.pi)
 
 
+FACES = {"top": 1, "bot": 2, "left": 3, "right": 4, "rear": 5, "front": 6}   # PPRTS_*_FACE, src/boxmc_geometry.F90:46-51
+
+
+def face_index(Nz, Nx, Ny, k, i, j, face):
+    """faceidx_by_cell_plus_offset (src/buildings.F90:217-222): the reference's 1-based linear index over [face_id, k, i, j] with
+    sizes [6, Nz, Nx, Ny], first dimension fastest.  k, i, j are 1-based cell indices as there; face is 1..6 or one of
+    "top", "bot", "left", "right", "rear", "front".  Arrays broadcast."""
+    f = np.vectorize(lambda v: FACES[v] if isinstance(v, str) else int(v), otypes=[np.int64])(face)
+    k, i, j = (np.asarray(a, dtype=np.int64) for a in (k, i, j))
+    if np.any((f < 1) | (f > 6) | (k < 1) | (k > Nz) | (i < 1) | (i > Nx) | (j < 1) | (j > Ny)):
+        raise ValueError("face_index: face id or cell out of range")
+    r = f + 6 * ((k - 1) + Nz * ((i - 1) + Nx * (j - 1)))
+    return int(r) if r.ndim == 0 else r
+
+
 class PprtsSolver:
     """One pprts solver (3_10) on one GPU, driven like the reference's Fortran/C API."""
 
@@ -280,6 +295,30 @@ class PprtsSolver:
         _lib.check(self.lib.tsx_pprts_get_result(self.h, _ptr(edn, np.float64)[0], _ptr(eup, np.float64)[0],
                                                  _ptr(abso, np.float64)[0], _ptr(edir, np.float64)[0], where))
         return edn, eup, abso, edir
+
+    # -- opt_buildings ------------------------------------------------------------------------------------
+    def set_buildings(self, faces, albedo, planck=None):
+        """tsx_pprts_set_buildings: faces = the reference's linear face indices (face_index), albedo per face (scalar
+        broadcasts), planck per face or None.  Call it before set_optical_properties; an empty face list detaches."""
+        faces = np.ascontiguousarray(np.atleast_1d(faces), dtype=np.int64)
+        n = faces.size
+        alb = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, dtype=np.float64), (n,)))
+        plk = None if planck is None else np.ascontiguousarray(np.broadcast_to(np.asarray(planck, dtype=np.float64), (n,)))
+        vp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        _lib.check(self.lib.tsx_pprts_set_buildings(self.h, n, vp(faces), vp(alb), vp(plk), 0))
+        self._nfaces = n
+
+    def get_buildings(self):
+        """tsx_pprts_get_buildings: (edir, incoming, outgoing) per face in W/m2, in the order of the face list"""
+        n = getattr(self, "_nfaces", 0)
+        edir, inc, out = (np.empty(max(n, 1)) for _ in range(3))
+        _lib.check(self.lib.tsx_pprts_get_buildings(self.h, C.c_void_p(edir.ctypes.data), C.c_void_p(inc.ctypes.data),
+                                                    C.c_void_p(out.ctypes.data), 0))
+        return edir[:n], inc[:n], out[:n]
+
+    def set_abso_in_buildings(self, val=None):
+        """-pprts_set_abso_in_buildings <val>: get_result returns val as the absorption of every building cell; None: off"""
+        _lib.check(self.lib.tsx_pprts_set_abso_in_buildings(self.h, int(val is not None), 0.0 if val is None else float(val)))
 
     def get_field(self, which):
         S, D = (3, 10) if self.core.D == 10 else (8, 16)
