@@ -494,8 +494,8 @@ int tsx_pool_check(int device, int reset, int64_t *out4);
  * would while the piece is live, then frees it (the free records the damage too).  No reference counterpart. */
 int tsx_pool_debug_overrun(int64_t bytes, int64_t off, int64_t nbytes, int64_t *out4);
 
-/* diagnostics: the code of one of libtsx's eight device code objects AS IT SITS IN DEVICE MEMORY (unit 0..7 = api, spmv310, spmv816,
- * pc, pcs, pcsflow, dedup, peer).  The unit's probe kernel reports its program counter in *pc_out and copies nwords 32-bit words from
+/* diagnostics: the code of one of libtsx's probed device code objects AS IT SITS IN DEVICE MEMORY (unit 0..10 = api, spmv310,
+ * spmv816, pc, pcs, pcsflow, dedup, peer, coeff, pipeline, diag).  The unit's probe kernel reports its program counter in *pc_out and copies nwords 32-bit words from
  * pc + delta to host_out (nwords = 0: the pc only); scripts/code_verify.py knows the units' ELF images inside libtsx.so and compares
  * every loaded .text byte with the file.  device < 0: the current device.  No reference counterpart. */
 int tsx_debug_code_read(int device, int unit, long long delta, long long nwords, void *host_out, unsigned long long *pc_out);

@@ -1,6 +1,6 @@
 """Compare libtsx's device code AS IT SITS IN DEVICE MEMORY with the bytes in the file (diagnostics, round 6).
 
-libtsx.so carries eight gfx950 code objects (one per translation unit, clang offload bundles in .hip_fatbin).  Every unit has a
+libtsx.so carries one gfx950 code object per translation unit (clang offload bundles in .hip_fatbin).  Every unit in UNITS has a
 probe kernel (TSX_CODE_PROBE, tenstream_amd/csrc/tsx_host.hpp) that reports its own program counter and copies words from
 pc + delta; this module knows each unit's ELF (section and symbol tables, the s_getpc_b64 inside the probe) and so can read back
 the unit's whole .text through `tsx_debug_code_read` and compare it byte for byte with the file.
@@ -15,7 +15,7 @@ import struct
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ["api", "spmv310", "spmv816", "pc", "pcs", "pcsflow", "dedup", "peer"]
+UNITS = ["api", "spmv310", "spmv816", "pc", "pcs", "pcsflow", "dedup", "peer", "coeff", "pipeline", "diag"]
 
 
 def _code_objects(blob):

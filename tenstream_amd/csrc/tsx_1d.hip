@@ -327,7 +327,7 @@ void tsx_gauss_legendre_01(int n, double *mu, double *w) {
 }
 
 // the atmosphere's fields as the handle holds them: with collapse the atmosphere-shaped scratch of set_optical_properties
-// (collapse_scratch, tsx_pipeline_api.inc: kabs, ksca, g, dz, planck at the head of ca_buf), else the solver's own copies
+// (collapse_scratch, tsx_pipeline.hip: kabs, ksca, g, dz, planck at the head of ca_buf), else the solver's own copies
 static int od_atm_fields(tsx_solver *s, const double **kabs, const double **ksca, const double **g, const double **dz, const double **planck) {
   const size_t ncol = (size_t)s->geo.ncol;
   if (s->collapse > 1) {

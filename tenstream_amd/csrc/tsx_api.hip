@@ -1,9 +1,6 @@
 // tsx_api.hip -- C-ABI of libtsx (see include/tsx.h).  Host orchestration: HIP streams/events,
 // device-resident Krylov loop (no host round trip per iteration), RCCL halo exchange.
 #include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,7 +17,6 @@
 #include "tsx_peer.hpp"
 #include "tsx_peer_dev.hpp"
 #include "tsx_kernels.hpp"
-#include "tsx_pipeline.hpp"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -164,7 +160,7 @@ extern "C" void tsx_default_ksp_opts(tsx_ksp_opts *o) {
   o->dtol = 1e4;    // PETSc KSP default divergence tolerance
   o->maxit = 1000;  // src/pprts_base.F90:1118
   o->pc = TSX_PC_REDBLACK;  // this back-end's default preconditioner
-  o->pc_sweeps = 0;  // automatic (prepare_ksp): 21 (22 passes) with the scan kernels, else 9
+  o->pc_sweeps = 0;  // automatic (tsx_prepare_ksp): 21 (22 passes) with the scan kernels, else 9
   o->check_every = 0;  // automatic: every 2 iterations (at most one enqueued in vain), the first look where the handle's previous solve ended (krylov_run); measured 1 / 2 / 3 / 4 / 6: 19.44 / 19.24 / 19.37 / 19.68 / 19.26 ms, warm start 3.40 / 3.47 / 3.58 / 3.69 / 3.82 ms
   o->fp32_directions = 2;
   o->pc_coeff_fp16 = 1;
@@ -184,33 +180,6 @@ extern "C" int tsx_determine_ksp_tolerances(const tsx_solver *s, double unconstr
     unconstrained_fraction = s->geo.Nz > 0 ? tsx_unconstrained_fraction(s) : 1.0;
   double a = 1e-4 * (double)s->grid.glob_xm * (double)s->grid.glob_ym * (double)(s->grid.Nz + 1) * unconstrained_fraction;
   *atol = a > 1e-8 ? a : 1e-8;
-  return TSX_OK;
-}
-
-static int create_fill(tsx_solver *s, const tsx_grid *grid);
-static void slots_free(tsx_solver *s);
-static void tsx_log_free(tsx_solver *s);
-extern "C" int tsx_create(const tsx_grid *grid, tsx_solver **out) {
-  ARGCHK(grid && out, "tsx_create: null argument");
-  ARGCHK(grid->solver_id == TSX_SOLVER_3_10 || grid->solver_id == TSX_SOLVER_8_16,
-         "tsx_create: solver_id must be 310 (3_10) or 816 (8_16)");
-  ARGCHK(grid->Nz >= 1 && grid->xm >= 1 && grid->ym >= 1, "tsx_create: empty grid");
-  ARGCHK(grid->nranks >= 1 && grid->rank >= 0 && grid->rank < grid->nranks, "tsx_create: bad rank/nranks");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) {
-    tsx_set_error("tsx_create: no HIP device available (libtsx has no CPU fallback)");
-    return TSX_ERR_NO_DEVICE;
-  }
-  tsx_solver *s = new tsx_solver();  // value-initialisation: every member zero, then the default member initialisers of tsx_internal.hpp
-  const int rc = create_fill(s, grid);
-  if (rc) {  // release the half-built solver (streams, events, buffers) on any failure
-    (void)tsx_destroy(s);
-    return rc;
-  }
-  if (const char *e = getenv("TSX_LOG"))
-    if (atoi(e) != 0) s->log = new TsxLog();
-  *out = s;
   return TSX_OK;
 }
 
@@ -288,6 +257,30 @@ static int create_fill(tsx_solver *s, const tsx_grid *grid) {
   return TSX_OK;
 }
 
+extern "C" int tsx_create(const tsx_grid *grid, tsx_solver **out) {
+  ARGCHK(grid && out, "tsx_create: null argument");
+  ARGCHK(grid->solver_id == TSX_SOLVER_3_10 || grid->solver_id == TSX_SOLVER_8_16,
+         "tsx_create: solver_id must be 310 (3_10) or 816 (8_16)");
+  ARGCHK(grid->Nz >= 1 && grid->xm >= 1 && grid->ym >= 1, "tsx_create: empty grid");
+  ARGCHK(grid->nranks >= 1 && grid->rank >= 0 && grid->rank < grid->nranks, "tsx_create: bad rank/nranks");
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev == 0) {
+    tsx_set_error("tsx_create: no HIP device available (libtsx has no CPU fallback)");
+    return TSX_ERR_NO_DEVICE;
+  }
+  tsx_solver *s = new tsx_solver();  // value-initialisation: every member zero, then the default member initialisers of tsx_internal.hpp
+  const int rc = create_fill(s, grid);
+  if (rc) {  // release the half-built solver (streams, events, buffers) on any failure
+    (void)tsx_destroy(s);
+    return rc;
+  }
+  if (const char *e = getenv("TSX_LOG"))
+    if (atoi(e) != 0) s->log = new TsxLog();
+  *out = s;
+  return TSX_OK;
+}
+
 extern "C" int tsx_destroy(tsx_solver *s) {
   if (!s) return TSX_OK;
   (void)hipSetDevice(s->device);
@@ -309,7 +302,7 @@ extern "C" int tsx_destroy(tsx_solver *s) {
     if (s->host_send[q]) (void)hipHostFree(s->host_send[q]);
     if (s->host_recv[q]) (void)hipHostFree(s->host_recv[q]);
   }
-  slots_free(s);
+  tsx_slots_free(s);
   tsx_buildings_free(s);
   tsx_log_free(s);
   delete s->flow_pr_shadow;
@@ -462,6 +455,61 @@ static int scalar_stage(tsx_solver *s, int nblocks, int nslots, int stage) {
   return TSX_OK;
 }
 
+// sum over the ranks of n (<= TSX_NSLOTS) host doubles, in place: RCCL through the device scalar block, or the host
+// callback (imp_allreduce_sum in the reference); a no-op on one rank
+int tsx_allreduce_host(tsx_solver *s, double *v, int n) {
+  if (s->grid.nranks <= 1) return TSX_OK;
+  ARGCHK(n <= TSX_NSLOTS, "allreduce_host: too many values");
+  if (tsx_peer_ready(s)) {
+    HIPCHK(hipMemcpyAsync(s->scal->red, v, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+    int rc = tsx_peer_allreduce(s, s->stream, s->scal->red, n, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(v, s->scal->red, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return tsx_peer_check(s);
+  }
+  if (s->allred_cb) {
+    double buf[TSX_NSLOTS] = {0};
+    memcpy(buf, v, sizeof(double) * n);
+    if (s->allred_cb(s->cb_ctx, buf, TSX_NSLOTS)) {
+      tsx_set_error("allreduce callback failed");
+      return TSX_ERR_COMM;
+    }
+    memcpy(v, buf, sizeof(double) * n);
+    return TSX_OK;
+  }
+  if (!s->comm_ready) {
+    tsx_set_error("nranks > 1 but neither tsx_comm_init nor tsx_comm_set_callbacks was called");
+    return TSX_ERR_STATE;
+  }
+  HIPCHK(hipMemcpyAsync(s->scal->red, v, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+  NCCLCHK(g_rccl.AllReduce(s->scal->red, s->scal->red, n, TSX_NCCL_FLOAT64, TSX_NCCL_SUM, s->nccl_comm, s->stream));
+  HIPCHK(hipMemcpyAsync(v, s->scal->red, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return TSX_OK;
+}
+// the same for one double that lives on the device (the direct sweep's residual), without leaving the stream on RCCL
+int tsx_allreduce_dev1(tsx_solver *s, double *d) {
+  if (s->grid.nranks <= 1) return TSX_OK;
+  if (tsx_peer_ready(s)) return tsx_peer_allreduce(s, s->stream, d, 1, nullptr);
+  if (s->allred_cb) {
+    double v = 0;
+    HIPCHK(hipMemcpyAsync(&v, d, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    int rc = tsx_allreduce_host(s, &v, 1);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(d, &v, sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return TSX_OK;
+  }
+  if (!s->comm_ready) {
+    tsx_set_error("nranks > 1 but neither tsx_comm_init nor tsx_comm_set_callbacks was called");
+    return TSX_ERR_STATE;
+  }
+  NCCLCHK(g_rccl.AllReduce(d, d, 1, TSX_NCCL_FLOAT64, TSX_NCCL_SUM, s->nccl_comm, s->stream));
+  return TSX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // workgroups of the layout conversion: one per tile of TSX_CV_TI columns x TSX_CV_TK levels of one row (grid-stride above 2^20)
 static int convert_grid(const TsxGeo &g) {
@@ -501,364 +549,14 @@ static int export_vec(tsx_solver *s, const double *v, double *ref_dev) {
   HIPCHK(hipGetLastError());
   return TSX_OK;
 }
+int tsx_export_vec(tsx_solver *s, const double *v, double *ref_dev) {
+  return s->geo.ntop == 2 ? export_vec<2, 4>(s, v, ref_dev) : export_vec<8, 4>(s, v, ref_dev);
+}
 
 static int ensure_stage(tsx_solver *s) {
   const size_t nb = (size_t)s->geo.N * sizeof(double);
   if (!s->stage_a) HIPCHK(tsx_dev_malloc((void **)&s->stage_a, nb));
   if (!s->stage_b) HIPCHK(tsx_dev_malloc((void **)&s->stage_b, nb));
-  return TSX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// l1d / a11 / a12 / albedo: shared by set_coeffs and set_optprop
-static int set_aux(tsx_solver *s, const uint8_t *l1d, const double *a11, const double *a12, const double *albedo, int where) {
-  const TsxGeo &g = s->geo;
-  const hipMemcpyKind mk = where == TSX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  std::vector<uint8_t> l1d_h(g.Nz);
-  if (where == TSX_HOST) memcpy(l1d_h.data(), l1d, g.Nz);
-  else HIPCHK(hipMemcpy(l1d_h.data(), l1d, g.Nz, hipMemcpyDeviceToHost));
-  s->any_l1d = false;
-  s->n1d = 0;
-  for (int k = 0; k < g.Nz; ++k) {
-    s->any_l1d |= l1d_h[k] != 0;
-    s->n1d += l1d_h[k] != 0;
-  }
-  HIPCHK(hipMemcpyAsync(s->l1d, l1d_h.data(), g.Nz, hipMemcpyHostToDevice, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  ARGCHK(!s->any_l1d || (a11 && a12), "a11/a12 required when any layer is 1-D");
-  HIPCHK(hipMemcpyAsync(s->albedo, albedo, sizeof(double) * g.ncol, mk, s->stream));
-  s->have_albedo = true;
-  if (s->any_l1d) {
-    if (!s->a11) HIPCHK(tsx_dev_malloc((void **)&s->a11, sizeof(double) * g.Nc));
-    if (!s->a12) HIPCHK(tsx_dev_malloc((void **)&s->a12, sizeof(double) * g.Nc));
-    TsxDevTmp g11, g12;
-    double *t11 = nullptr, *t12 = nullptr;
-    const double *p11 = a11, *p12 = a12;
-    if (where == TSX_HOST) {
-      HIPCHK(g11.alloc(sizeof(double) * g.Nc));
-      HIPCHK(g12.alloc(sizeof(double) * g.Nc));
-      t11 = g11.as<double>();
-      t12 = g12.as<double>();
-      HIPCHK(hipMemcpyAsync(t11, a11, sizeof(double) * g.Nc, hipMemcpyHostToDevice, s->stream));
-      HIPCHK(hipMemcpyAsync(t12, a12, sizeof(double) * g.Nc, hipMemcpyHostToDevice, s->stream));
-      p11 = t11;
-      p12 = t12;
-    }
-    hipLaunchKernelGGL(tsx_k_import_cellfield, dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g, p11, s->a11);
-    hipLaunchKernelGGL(tsx_k_import_cellfield, dim3(grid_for(g.Nc)), dim3(TSX_BLOCK), 0, s->stream, g, p12, s->a12);
-    HIPCHK(hipStreamSynchronize(s->stream));
-  }
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return TSX_OK;
-}
-
-static int ensure_coef_storage(tsx_solver *s, int out_bytes) {
-  const size_t ncoef = (size_t)s->geo.D * s->geo.D * s->geo.Nc;
-  if (s->coef && s->coef_bytes != out_bytes) {
-    HIPCHK(tsx_dev_free(s->coef));
-    s->coef = nullptr;
-  }
-  if (!s->coef) HIPCHK(tsx_dev_malloc(&s->coef, ncoef * out_bytes));
-  s->coef_bytes = out_bytes;
-  return TSX_OK;
-}
-
-extern "C" int tsx_diff_set_coeffs(tsx_solver *s, const void *diff2diff, int coeff_kind, const uint8_t *l1d,
-                                   const double *a11, const double *a12, const double *albedo, int where) {
-  ARGCHK(s && diff2diff && l1d && albedo, "tsx_diff_set_coeffs: null argument");
-  ARGCHK(coeff_kind == 4 || coeff_kind == 8, "tsx_diff_set_coeffs: coeff_kind must be 4 or 8");
-  if (int rc_c = tsx_refuse_collapsed(s, "tsx_diff_set_coeffs")) return rc_c;
-  HIPCHK(hipSetDevice(s->device));
-  const TsxGeo &g = s->geo;
-  const int DD = g.D * g.D;
-  const size_t ncoef = (size_t)DD * g.Nc;
-  int rc = set_aux(s, l1d, a11, a12, albedo, where);
-  if (rc) return rc;
-
-  const void *src_dev = diff2diff;
-  TsxDevTmp tmp, flag_guard;  // released on every exit path (one call per g-point: a leak here is 3.4 GB per call)
-  if (where == TSX_HOST) {
-    HIPCHK(tmp.alloc(ncoef * coeff_kind));
-    HIPCHK(hipMemcpyAsync(tmp.p, diff2diff, ncoef * coeff_kind, hipMemcpyHostToDevice, s->stream));
-    src_dev = tmp.p;
-  }
-  int out_bytes = 4;
-  if (coeff_kind == 8) {  // keep fp64 unless every value survives the round trip through fp32
-    HIPCHK(flag_guard.alloc(sizeof(int)));
-    int *flag = flag_guard.as<int>();
-    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s->stream));
-    hipLaunchKernelGGL(tsx_k_check_fp32_lossless, dim3(grid_for((long long)ncoef)), dim3(TSX_BLOCK), 0, s->stream,
-                       (long long)ncoef, (const double *)src_dev, flag);
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    out_bytes = bad ? 8 : 4;
-  }
-  if ((rc = ensure_coef_storage(s, out_bytes))) return rc;
-  const int TI = DD > 128 ? 16 : 32;  // keep the LDS tile under 64 KiB for D = 16
-  const int nbk = grid_for((long long)((g.xm + TI - 1) / TI) * g.ym * g.Nz * TSX_BLOCK, 8192);
-  const size_t lds = (size_t)TI * (DD + 1) * out_bytes;
-  if (coeff_kind == 8 && out_bytes == 8)
-    hipLaunchKernelGGL((tsx_k_import_coeff<double, double>), dim3(nbk), dim3(TSX_BLOCK), lds, s->stream, g, DD, TI,
-                       (const double *)src_dev, (double *)s->coef);
-  else if (coeff_kind == 8)
-    hipLaunchKernelGGL((tsx_k_import_coeff<double, float>), dim3(nbk), dim3(TSX_BLOCK), lds, s->stream, g, DD, TI,
-                       (const double *)src_dev, (float *)s->coef);
-  else
-    hipLaunchKernelGGL((tsx_k_import_coeff<float, float>), dim3(nbk), dim3(TSX_BLOCK), lds, s->stream, g, DD, TI,
-                       (const float *)src_dev, (float *)s->coef);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  s->have_coeffs = true;
-  s->coef_h_valid = false;
-  s->pcx_valid = false;
-  s->dd_valid = false;
-  s->dd_on = false;
-  s->dd_pc = false;
-  s->dd_from_coords = false;
-  s->dd_hash_ready = false;  // imported blocks: tsx_dedup.hip hashes them itself
-  s->coef_dense_valid = true;
-  return TSX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// LUT on the device
-// axes of LUT_3_10 / LUT_8_16 diffuse tables (src/optprop_base.F90:200-212, 228-240): presets from
-// src/optprop_parameters.F90:145-154 (tau31), :194-199 (w020), :107-110 (aspect23), :245 (g6)
-static const float k_preset_tau31[31] = {
-    1e-10f, 3.62266272998e-07f, 7.04565803675e-06f, 4.47545500233e-05f, 0.000172126759821f, 0.000495994753047f,
-    0.00119161313679f, 0.00251026980343f, 0.00480799264297f, 0.00856221891924f, 0.0143961482731f, 0.0231530284254f,
-    0.0358868239775f, 0.0541358315379f, 0.079959118223f, 0.11623968405f, 0.167882053841f, 0.246414427244f,
-    0.350199325489f, 0.502459974196f, 0.759082408765f, 1.08083180518f, 1.5415157991f, 2.19832932733f, 3.04549626819f,
-    4.27145477454f, 6.16953841432f, 9.43719309835f, 15.7335501106f, 29.5819342206f, 100.0f};
-static const float k_preset_w020[20] = {
-    0.0f, 0.152960717624f, 0.295085090042f, 0.416951893959f, 0.521358613652f, 0.610087211908f, 0.684967634054f,
-    0.747886390181f, 0.800286677013f, 0.84336972609f, 0.878674797098f, 0.906377786525f, 0.928097831502f,
-    0.943463164595f, 0.954135786554f, 0.963824066888f, 0.972632134967f, 0.981529289348f, 0.990759644674f, 0.99999f};
-static const float k_preset_aspect23[23] = {0.02f, 0.032f, 0.042f, 0.056f, 0.075f, 0.1f, 0.133f, 0.178f, 0.237f, 0.316f,
-                                            0.422f, 0.562f, 0.75f, 1.f, 1.25f, 1.562f, 1.953f, 2.441f, 3.052f, 3.815f,
-                                            4.768f, 5.96f, 7.451f};
-static const float k_preset_g6[6] = {0.0f, 0.2424f, 0.4137f, 0.5717f, 0.7144f, 0.85f};
-
-extern "C" int tsx_lut_set_diffuse(tsx_solver *s, const float *table, int32_t nvec, int64_t nentries, int32_t ndim,
-                                   const int32_t *n, const float *axes_concat, int where) {
-  ARGCHK(s && table && n && axes_concat, "tsx_lut_set_diffuse: null argument");
-  ARGCHK(ndim == 4, "tsx_lut_set_diffuse: diffuse tables have 4 dimensions (tau, w0, aspect_zx, g)");
-  ARGCHK(nvec == s->geo.D * s->geo.D, "tsx_lut_set_diffuse: nvec must be D*D");
-  long long prod = 1, nax = 0;
-  for (int d = 0; d < ndim; ++d) {
-    ARGCHK(n[d] >= 1, "tsx_lut_set_diffuse: empty axis");
-    prod *= n[d];
-    nax += n[d];
-  }
-  ARGCHK(prod == nentries, "tsx_lut_set_diffuse: nentries != product of axis lengths");
-  HIPCHK(hipSetDevice(s->device));
-  TsxLutHost &L = s->lut_diff;
-  if (L.d_axes) HIPCHK(tsx_dev_free(L.d_axes));
-  if (L.d_table) HIPCHK(tsx_dev_free(L.d_table));
-  L = TsxLutHost();
-  HIPCHK(tsx_dev_malloc((void **)&L.d_axes, sizeof(float) * nax));
-  HIPCHK(tsx_dev_malloc((void **)&L.d_table, sizeof(float) * (size_t)nvec * nentries));
-  const hipMemcpyKind mk = where == TSX_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  HIPCHK(hipMemcpy(L.d_axes, axes_concat, sizeof(float) * nax, mk));
-  HIPCHK(hipMemcpy(L.d_table, table, sizeof(float) * (size_t)nvec * nentries, mk));
-  L.ndim = ndim;
-  L.nvec = nvec;
-  L.nentries = nentries;
-  for (int d = 0; d < ndim; ++d) L.n[d] = n[d];
-  L.ready = true;
-  return TSX_OK;
-}
-
-extern "C" int tsx_lut_load_diffuse_mmap4(tsx_solver *s, const char *path) {
-  ARGCHK(s && path, "tsx_lut_load_diffuse_mmap4: null argument");
-  // src/mmap.F90:129-203: header = one page of size_t, data starts at the page boundary
-  const long pagesize = sysconf(_SC_PAGESIZE);
-  int fd = open(path, O_RDONLY);
-  if (fd < 0) {
-    tsx_set_error(std::string("tsx_lut_load_diffuse_mmap4: cannot open ") + path);
-    return TSX_ERR_ARG;
-  }
-  std::vector<size_t> header((size_t)pagesize / sizeof(size_t));
-  if (read(fd, header.data(), (size_t)pagesize) != pagesize) {
-    close(fd);
-    tsx_set_error("tsx_lut_load_diffuse_mmap4: short header");
-    return TSX_ERR_ARG;
-  }
-  const size_t dtype_size = header[0], n_elems = header[1], n_bytes = header[2], dim1 = header[3], dim2 = header[4];
-  if (dtype_size != 4 || n_bytes != 4 * n_elems || dim1 * dim2 != n_elems || header[5] != 0) {
-    close(fd);
-    tsx_set_error("tsx_lut_load_diffuse_mmap4: not a 2-D real32 mmap4 table");
-    return TSX_ERR_ARG;
-  }
-  void *m = mmap(nullptr, n_bytes + (size_t)pagesize, PROT_READ, MAP_PRIVATE | MAP_NORESERVE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) {
-    tsx_set_error("tsx_lut_load_diffuse_mmap4: mmap failed");
-    return TSX_ERR_ARG;
-  }
-  const int32_t n[4] = {31, 20, 23, 6};
-  std::vector<float> axes;
-  axes.insert(axes.end(), k_preset_tau31, k_preset_tau31 + 31);
-  axes.insert(axes.end(), k_preset_w020, k_preset_w020 + 20);
-  axes.insert(axes.end(), k_preset_aspect23, k_preset_aspect23 + 23);
-  axes.insert(axes.end(), k_preset_g6, k_preset_g6 + 6);
-  int rc = tsx_lut_set_diffuse(s, (const float *)((const char *)m + pagesize), (int32_t)dim1, (int64_t)dim2, 4, n,
-                               axes.data(), TSX_HOST);
-  munmap(m, n_bytes + (size_t)pagesize);
-  return rc;
-}
-
-// the cells' LUT coordinates in cell order (tsx_k_cell_samples) -> s->cell_samp; TSX_CELL_SAMPLES=0: the coefficient kernels read
-// the level-fastest arrays themselves
-int tsx_cell_samples(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx) {
-  const TsxGeo &gm = s->geo;
-  const char *e = getenv("TSX_CELL_SAMPLES");
-  if (e && atoi(e) == 0) {
-    if (s->cell_samp) (void)tsx_dev_free(s->cell_samp);
-    s->cell_samp = nullptr;
-    return TSX_OK;
-  }
-  if (!s->cell_samp) HIPCHK(tsx_dev_malloc(&s->cell_samp, sizeof(float4) * (size_t)gm.Nc));
-  s->cell_samp_src[0] = kabs, s->cell_samp_src[1] = ksca, s->cell_samp_src[2] = g, s->cell_samp_src[3] = dz;
-  s->cell_samp_dx = dx;
-  hipLaunchKernelGGL(tsx_k_cell_samples, dim3((gm.ncol + 31) / 32, (gm.Nz + 31) / 32), dim3(TSX_BLOCK), 0, s->stream, gm, kabs, ksca, g, dz,
-                     dx, (float4 *)s->cell_samp);
-  HIPCHK(hipGetLastError());
-  return TSX_OK;
-}
-
-// alloc_coeff_diff2diff on the device: kabs/ksca/g/dz are device pointers in the reference layout
-// buildings (tsx_pprts_set_optical_properties with buildings attached only; the seam entries ignore them): the blocks are patched
-// in the dense planes BEFORE anything is shared, so the coordinate-keyed sharing -- which never writes dense planes and whose
-// "previous grouping still exact" reuse (TSX_DEDUP_REUSE) looks at coordinates alone -- is skipped, and the block-based build
-// (tsx_dedup_ensure) groups the patched blocks by their renewed hashes and an exact compare
-static int lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx,
-                              bool buildings = false) {
-  TsxLogScope log_scope(s, TSX_EV_GET_COEFF_DIFF2DIFF);  // get_coeff_diff2diff, src/pprts.F90:3422-3489
-  const TsxGeo &gm = s->geo;
-  // a new coefficient set: whatever the shared storage held is gone (the callers used to reset these after the launch; the
-  // coordinate-keyed build below sets them itself)
-  s->dd_valid = false;
-  s->dd_on = false;
-  s->dd_pc = false;
-  s->coef_dense_valid = true;
-  s->dd_blocks_patched = false;
-  TsxLutDev L;
-  memset(&L, 0, sizeof(L));
-  const TsxLutHost &H = s->lut_diff;
-  L.ndim = H.ndim;
-  L.nvec = H.nvec;
-  long long off = 1;
-  int aoff = 0;
-  for (int d = 0; d < H.ndim; ++d) {
-    L.n[d] = H.n[d];
-    L.axis_off[d] = aoff;
-    aoff += H.n[d];
-    L.offs[d] = off;
-    off *= H.n[d];
-  }
-  L.axes = H.d_axes;
-  L.table = H.d_table;
-  int rcs = tsx_cell_samples(s, kabs, ksca, g, dz, dx);
-  if (rcs) return rcs;
-  // sharing keyed on the cells' LUT coordinates, before anything is interpolated (tsx_dedup.hip "coordinates first"): where
-  // it pays only the distinct tuples are interpolated, straight into the shared storage, and no dense planes are written
-  if (!buildings) {
-    bool built = false;
-    int rc = tsx_dedup_from_coords(s, L, &built);
-    if (rc) return rc;
-    if (built) return TSX_OK;
-  } else {
-    s->dd_from_coords = false;  // no grouping by coordinates is current, none is taken over by the next set
-  }
-  unsigned long long *hash = nullptr;  // the kernel leaves the blocks' hashes for the shared storage (tsx_dedup.hip)
-  {
-    int rc = tsx_dedup_hash_buffer(s, &hash);
-    if (rc) return rc;
-  }
-  const int nbk = grid_for(gm.Nc, 8192);
-  const float4 *samp = (const float4 *)s->cell_samp;
-  if (gm.D == 10)
-    hipLaunchKernelGGL((tsx_k_lut_diff2diff<100>), dim3(nbk), dim3(TSX_BLOCK), 0, s->stream, gm, L, kabs, ksca, g, dz, dx,
-                       s->l1d, (float *)s->coef, hash, samp);
-  else
-    hipLaunchKernelGGL((tsx_k_lut_diff2diff<256>), dim3(nbk), dim3(TSX_BLOCK), 0, s->stream, gm, L, kabs, ksca, g, dz, dx,
-                       s->l1d, (float *)s->coef, hash, samp);
-  s->dd_hash_ready = hash != nullptr;
-  if (buildings) {
-    int rc = tsx_buildings_patch_diffuse(s, hash);
-    if (rc) return rc;
-    s->dd_blocks_patched = true;
-  }
-  return TSX_OK;
-}
-
-extern "C" int tsx_diff_set_optprop(tsx_solver *s, const double *kabs, const double *ksca, const double *g,
-                                    const double *dz, double dx, const uint8_t *l1d, const double *a11, const double *a12,
-                                    const double *albedo, int where) {
-  ARGCHK(s && kabs && ksca && g && dz && l1d && albedo, "tsx_diff_set_optprop: null argument");
-  ARGCHK(dx > 0, "tsx_diff_set_optprop: dx <= 0");
-  if (int rc_c = tsx_refuse_collapsed(s, "tsx_diff_set_optprop")) return rc_c;
-  if (!s->lut_diff.ready) {
-    tsx_set_error("tsx_diff_set_optprop: load the diffuse LUT first (tsx_lut_set_diffuse / tsx_lut_load_diffuse_mmap4)");
-    return TSX_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(s->device));
-  const TsxGeo &gm = s->geo;
-  int rc = set_aux(s, l1d, a11, a12, albedo, where);
-  if (rc) return rc;
-  if ((rc = ensure_coef_storage(s, 4))) return rc;
-  const size_t nb = sizeof(double) * gm.Nc;
-  const double *p[4] = {kabs, ksca, g, dz};
-  TsxDevTmp tmp[4];
-  if (where == TSX_HOST) {
-    for (int q = 0; q < 4; ++q) {
-      HIPCHK(tmp[q].alloc(nb));
-      HIPCHK(hipMemcpyAsync(tmp[q].p, p[q], nb, hipMemcpyHostToDevice, s->stream));
-      p[q] = tmp[q].as<double>();
-    }
-  }
-  if ((rc = lut_diffuse_launch(s, p[0], p[1], p[2], p[3], dx))) return rc;  // (resets / sets the shared-storage state)
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  s->have_coeffs = true;
-  s->coef_h_valid = false;
-  s->pcx_valid = false;
-  return TSX_OK;
-}
-
-extern "C" int tsx_diff_get_coeffs(tsx_solver *s, double *diff2diff, int where) {
-  ARGCHK(s && diff2diff, "tsx_diff_get_coeffs: null argument");
-  if (!s->have_coeffs) {
-    tsx_set_error("tsx_diff_get_coeffs: no coefficients set");
-    return TSX_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(s->device));
-  {
-    int rc = tsx_coef_ensure_dense(s);  // the LUT path may have left the blocks in the shared storage only
-    if (rc) return rc;
-  }
-  const TsxGeo &g = s->geo;
-  const int DD = g.D * g.D;
-  const size_t ncoef = (size_t)DD * g.Nc;
-  double *out = diff2diff;
-  TsxDevTmp tmp_guard;
-  double *tmp = nullptr;
-  if (where == TSX_HOST) {
-    HIPCHK(tmp_guard.alloc(ncoef * sizeof(double)));
-    tmp = tmp_guard.as<double>();
-    out = tmp;
-  }
-  if (s->coef_bytes == 4)
-    hipLaunchKernelGGL((tsx_k_export_coeff<float>), dim3(grid_for((long long)ncoef, 8192)), dim3(TSX_BLOCK), 0, s->stream, g,
-                       DD, (const float *)s->coef, out);
-  else
-    hipLaunchKernelGGL((tsx_k_export_coeff<double>), dim3(grid_for((long long)ncoef, 8192)), dim3(TSX_BLOCK), 0, s->stream, g,
-                       DD, (const double *)s->coef, out);
-  HIPCHK(hipGetLastError());
-  if (where == TSX_HOST) HIPCHK(hipMemcpyAsync(diff2diff, tmp, ncoef * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
   return TSX_OK;
 }
 
@@ -1208,8 +906,6 @@ static int krylov_run(tsx_solver *s, const tsx_ksp_opts *o) {
   return TSX_OK;
 }
 
-static int prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o);
-
 // The reference's failure path (src/pprts.F90:4277-4302): a solve that ends with a non-positive reason is repeated once from
 // a zero initial guess with a second, more conservative solver (there: GMRES on the same preconditioner); only if that
 // fails too the negative reason is reported (and the caller aborts).  Here the second solver is the same flexible
@@ -1290,10 +986,10 @@ static int krylov_run_with_retry(tsx_solver *s, tsx_ksp_opts *o) {
   tsx_ksp_opts o2 = *o;
   o2.fp32_directions = 0;
   o2.pc_coeff_fp16 = 0;
-  o2.pc = TSX_PC_REDBLACK;  // on the exact blocks (tsx_pcx.hip, 3_10 and 8_16); zebra rows on odd grids (prepare_ksp)
+  o2.pc = TSX_PC_REDBLACK;  // on the exact blocks (tsx_pcx.hip, 3_10 and 8_16); zebra rows on odd grids (tsx_prepare_ksp)
   o2.pc_sweeps = 0;         // ... with that path's own pass count
   tsx_ksp_opts o3;
-  if ((rc = prepare_ksp(s, &o2, &o3))) return rc;
+  if ((rc = tsx_prepare_ksp(s, &o2, &o3))) return rc;
   HIPCHK(hipMemsetAsync(s->vx, 0, sizeof(double) * (size_t)s->geo.N, s->stream));
   s->x_is_zero = true;
   hipEvent_t keep0 = s->ev0;  // solve_ms covers both attempts: keep the first start event
@@ -1309,8 +1005,11 @@ static int krylov_run_with_retry(tsx_solver *s, tsx_ksp_opts *o) {
   s->scal_host->its += its_first;  // Niter_diff counts the work of both attempts
   return TSX_OK;
 }
+int tsx_krylov_run_with_retry(tsx_solver *s, tsx_ksp_opts *o) {
+  return s->geo.ntop == 2 ? krylov_run_with_retry<2, 4>(s, o) : krylov_run_with_retry<8, 4>(s, o);
+}
 
-static int fill_result(tsx_solver *s, tsx_ksp_result *res) {
+int tsx_fill_result(tsx_solver *s, tsx_ksp_result *res) {
   {
     int rc = tsx_peer_check(s);  // the stream has been synchronised: did a bounded wait of the peer transport expire?
     if (rc) return rc;
@@ -1327,8 +1026,6 @@ static int fill_result(tsx_solver *s, tsx_ksp_result *res) {
   HIPCHK(hipEventElapsedTime(&res->solve_ms, s->ev0, s->ev1));
   return TSX_OK;
 }
-
-static int allreduce_host(tsx_solver *s, double *v, int n);  // tsx_pipeline_api.inc
 
 template <int NTOP, int NSIDE>
 static int diff_solve_t(tsx_solver *s, const double *b, double *x, int where, const tsx_ksp_opts *o,
@@ -1359,7 +1056,7 @@ static int diff_solve_t(tsx_solver *s, const double *b, double *x, int where, co
     HIPCHK(hipMemcpyAsync(&nz, nzflag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     double anynz = nz;
-    if (s->grid.nranks > 1 && (rc = allreduce_host(s, &anynz, 1))) return rc;  // zero only if zero on every rank
+    if (s->grid.nranks > 1 && (rc = tsx_allreduce_host(s, &anynz, 1))) return rc;  // zero only if zero on every rank
     s->x_is_zero = anynz == 0.0;
   }
   HIPCHK(hipEventRecord(e_imp1, s->stream));
@@ -1375,14 +1072,14 @@ static int diff_solve_t(tsx_solver *s, const double *b, double *x, int where, co
   HIPCHK(hipStreamSynchronize(s->stream));
 
   if (res) {
-    if ((rc = fill_result(s, res))) return rc;
+    if ((rc = tsx_fill_result(s, res))) return rc;
     HIPCHK(hipEventElapsedTime(&res->import_ms, e_imp0, e_imp1));
     HIPCHK(hipEventElapsedTime(&res->export_ms, s->ev1, e_exp1));
   }
   return TSX_OK;
 }
 
-static int prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o) {
+int tsx_prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o) {
   TsxLogScope log_scope(s, TSX_EV_SETUP_MDIFF);  // setup_Mdiff, src/pprts.F90:2952-2954: here the packing / sharing of the coefficient set
   if (opts) *o = *opts;
   else tsx_default_ksp_opts(o);
@@ -1462,7 +1159,7 @@ extern "C" int tsx_diff_solve(tsx_solver *s, const double *b, double *x, int whe
   }
   tsx_ksp_opts o;
   {
-    int rc = prepare_ksp(s, opts, &o);
+    int rc = tsx_prepare_ksp(s, opts, &o);
     if (rc) return rc;
   }
   return s->geo.ntop == 2 ? diff_solve_t<2, 4>(s, b, x, where, &o, res) : diff_solve_t<8, 4>(s, b, x, where, &o, res);
@@ -1514,7 +1211,7 @@ extern "C" int tsx_diff_pc_apply(tsx_solver *s, const double *v, double *z, int 
   HIPCHK(hipSetDevice(s->device));
   s->pc = pc;
   s->pc_sweeps = pc_sweeps;
-  if (s->pc == TSX_PC_REDBLACK) {  // same eligibility rule as prepare_ksp
+  if (s->pc == TSX_PC_REDBLACK) {  // same eligibility rule as tsx_prepare_ksp
     const TsxGeo &g = s->geo;
     if (!((mixed && g.xm % 2 == 0 && g.xm >= 2 && (!g.wrap_y || g.ym % 2 == 0)) || (!mixed && tsx_pcx_eligible(s)))) s->pc = TSX_PC_ZEBRA;
   }
@@ -1627,7 +1324,7 @@ static int bench_kernel_t(tsx_solver *s, int kernel, int reps, float *avg_ms) {
     // 3 = one intermediate Gauss-Seidel pass of the scan kernels as a launch of its own, 4 = the flow kernel: the intermediate
     // passes of an application in one launch, as the Krylov loop issues it (the vector update before it has left the bf16 words)
     tsx_ksp_opts o, ou;
-    if ((rc = prepare_ksp(s, nullptr, &o))) return rc;
+    if ((rc = tsx_prepare_ksp(s, nullptr, &o))) return rc;
     (void)ou;
     s->pc_rhs = s->p32;
     if (kernel >= 3 && !s->coef_h_scan) {
@@ -1750,245 +1447,5 @@ extern "C" int tsx_pc_info(const tsx_solver *s, int32_t *pc, int32_t *pc_sweeps,
   *scan = s->coef_h_scan ? (s->pcr_on ? 3 : 1) : 0;  // bit 1: identical recurrence records are stored once (tsx_records_share)
   return TSX_OK;
 }
-
-// ---- bandwidth probes: what this device's memory system delivers to plain streaming kernels, as a ceiling to report the
-// rooflines against beside the nominal 8 TB/s (MI355X_MICROARCH.md: about 6.3 TB/s achievable).  U independent 16-byte
-// accesses per lane in flight, a capped grid with a grid-stride loop, optionally non-temporal; the best variant counts.
-typedef float tsx_f4v __attribute__((ext_vector_type(4)));  // a native vector: the non-temporal builtins take no HIP_vector_type
-template <int U, bool NT>
-__global__ __launch_bounds__(TSX_BLOCK) void tsx_k_copy16u(long long n, const tsx_f4v *__restrict__ a, tsx_f4v *__restrict__ b) {
-  const long long stride = (long long)gridDim.x * TSX_BLOCK;
-  long long q = (long long)blockIdx.x * TSX_BLOCK + threadIdx.x;
-  for (; q + (U - 1) * stride < n; q += U * stride) {
-    tsx_f4v v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = NT ? __builtin_nontemporal_load(&a[q + u * stride]) : a[q + u * stride];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (NT) __builtin_nontemporal_store(v[u], &b[q + u * stride]);
-      else b[q + u * stride] = v[u];
-    }
-  }
-  for (; q < n; q += stride) b[q] = a[q];
-}
-template <int U, bool NT>
-__global__ __launch_bounds__(TSX_BLOCK) void tsx_k_read16u(long long n, const tsx_f4v *__restrict__ a, float *__restrict__ out) {
-  const long long stride = (long long)gridDim.x * TSX_BLOCK;
-  long long q = (long long)blockIdx.x * TSX_BLOCK + threadIdx.x;
-  float acc = 0.0f;
-  for (; q + (U - 1) * stride < n; q += U * stride) {
-    tsx_f4v v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = NT ? __builtin_nontemporal_load(&a[q + u * stride]) : a[q + u * stride];
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
-  }
-  for (; q < n; q += stride) acc += a[q][0];
-  if (acc == 123.456f) out[blockIdx.x] = acc;  // keeps the loads alive; the buffer holds a different constant
-}
-
-// best copy (read + write bytes) and best read rate over the variants, GB/s; variant ids for the record
-static int probe_bandwidth(tsx_solver *s, size_t bytes, int reps, double *copy_gbps, double *read_gbps, int *copy_variant,
-                           int *read_variant) {
-  HIPCHK(hipSetDevice(s->device));
-  TsxDevTmp A, B;
-  HIPCHK(A.alloc(bytes));
-  HIPCHK(B.alloc(bytes));
-  HIPCHK(hipMemsetAsync(A.p, 1, bytes, s->stream));
-  HIPCHK(hipMemsetAsync(B.p, 0, bytes, s->stream));
-  const long long n = (long long)(bytes / 16);
-  const tsx_f4v *a = A.as<tsx_f4v>();
-  tsx_f4v *b = B.as<tsx_f4v>();
-  const int grids[3] = {2048, 4096, 16384};
-  double best_c = 0, best_r = 0;
-  int vc = -1, vr = -1;
-  auto timed = [&](auto launch, double moved, double *best, int *bv, int id) -> int {
-    launch();  // warm
-    HIPCHK(hipEventRecord(s->ev0, s->stream));
-    for (int q = 0; q < reps; ++q) launch();
-    HIPCHK(hipEventRecord(s->ev1, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    const double g = moved * reps / (ms * 1e-3) / 1e9;
-    if (g > *best) {
-      *best = g;
-      *bv = id;
-    }
-    return TSX_OK;
-  };
-  int rc;
-  for (int gi = 0; gi < 3; ++gi) {
-    const int nb = (int)(n / TSX_BLOCK < grids[gi] ? (n / TSX_BLOCK > 0 ? n / TSX_BLOCK : 1) : grids[gi]);
-#define TSX_PROBE(U, NT, ID)                                                                                                        \
-  if ((rc = timed([&] { hipLaunchKernelGGL((tsx_k_copy16u<U, NT>), dim3(nb), dim3(TSX_BLOCK), 0, s->stream, n, a, b); },            \
-                  2.0 * (double)(n * 16), &best_c, &vc, gi * 10 + ID)))                                                             \
-    return rc;                                                                                                                      \
-  if ((rc = timed([&] { hipLaunchKernelGGL((tsx_k_read16u<U, NT>), dim3(nb), dim3(TSX_BLOCK), 0, s->stream, n, a, (float *)b); },   \
-                  (double)(n * 16), &best_r, &vr, gi * 10 + ID)))                                                                   \
-    return rc;
-    TSX_PROBE(1, false, 0)
-    TSX_PROBE(4, false, 1)
-    TSX_PROBE(8, false, 2)
-    TSX_PROBE(4, true, 3)
-    TSX_PROBE(8, true, 4)
-#undef TSX_PROBE
-  }
-  HIPCHK(hipGetLastError());
-  *copy_gbps = best_c;
-  *read_gbps = best_r;
-  if (copy_variant) *copy_variant = vc;
-  if (read_variant) *read_variant = vr;
-  return TSX_OK;
-}
-
-extern "C" int tsx_probe_copy_bandwidth(tsx_solver *s, size_t bytes, int reps, double *gbps) {
-  ARGCHK(s && gbps && reps >= 1 && bytes >= 16, "tsx_probe_copy_bandwidth: bad argument");
-  double r = 0;
-  return probe_bandwidth(s, bytes, reps, gbps, &r, nullptr, nullptr);
-}
-// out4: best copy GB/s (bytes read + written), best read GB/s, and the variants that gave them (grid index * 10 + kernel id:
-// kernel 0 one access per lane, 1 / 2 four / eight in flight, 3 / 4 the same non-temporal; grids 2048, 4096, 16384 workgroups)
-extern "C" int tsx_probe_bandwidth(tsx_solver *s, size_t bytes, int reps, double *out4) {
-  ARGCHK(s && out4 && reps >= 1 && bytes >= 16, "tsx_probe_bandwidth: bad argument");
-  int vc = -1, vr = -1;
-  int rc = probe_bandwidth(s, bytes, reps, &out4[0], &out4[1], &vc, &vr);
-  out4[2] = vc;
-  out4[3] = vr;
-  return rc;
-}
-
-// ---- log events + roctx ranges (TsxLog, tsx_internal.hpp).  roctx comes from librocprofiler-sdk-roctx (ROCm 7; libroctx64 before
-// it), bound at run time on first use: libtsx links neither, and without the library the ranges are no-ops.
-static const char *const kLogNames[TSX_EV_TOTAL] = {"set_optprop", "get_coeff_diff2diff", "get_coeff_dir2dir", "compute_Edir", "solve_Mdir",
-                                                   "setup_diff_src", "compute_Ediff", "setup_Mdiff", "solve_Mdiff", "compute_absorption",
-                                                   "get_result", "solve_twostream", "solve_schwarzschild"};
-struct TsxRoctx {
-  int (*push)(const char *) = nullptr;
-  int (*pop)() = nullptr;
-  TsxRoctx() {
-    void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) return;
-    push = (int (*)(const char *))dlsym(h, "roctxRangePushA");
-    pop = (int (*)())dlsym(h, "roctxRangePop");
-    if (!push || !pop) push = nullptr, pop = nullptr;
-  }
-};
-static TsxRoctx &tsx_roctx() {
-  static TsxRoctx r;
-  return r;
-}
-static void tsx_log_retire(tsx_solver *s, bool wait) {
-  TsxLog *L = s->log;
-  size_t keep = 0;
-  for (size_t q = 0; q < L->pending.size(); ++q) {
-    TsxLogPending &p = L->pending[q];
-    bool ready = hipEventQuery(p.b) == hipSuccess;
-    if (!ready && wait) ready = hipEventSynchronize(p.b) == hipSuccess;
-    float ms = 0;
-    if (ready && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-      L->ms[p.ev] += ms;
-      L->pool.push_back(p.a);
-      L->pool.push_back(p.b);
-    } else if (ready) {  // (an event pair that cannot be read: drop it)
-      (void)hipEventDestroy(p.a);
-      (void)hipEventDestroy(p.b);
-    } else {
-      L->pending[keep++] = p;
-    }
-  }
-  L->pending.resize(keep);
-  (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error of the caller
-}
-static hipEvent_t tsx_log_event(TsxLog *L) {
-  hipEvent_t e = nullptr;
-  if (!L->pool.empty()) {
-    e = L->pool.back();
-    L->pool.pop_back();
-  } else if (hipEventCreate(&e) != hipSuccess) {
-    e = nullptr;
-  }
-  return e;
-}
-void tsx_log_begin(tsx_solver *s, int ev, hipEvent_t *a) {
-  TsxRoctx &r = tsx_roctx();
-  if (r.push) r.push(kLogNames[ev]);
-  *a = tsx_log_event(s->log);
-  if (*a) (void)hipEventRecord(*a, s->stream);
-}
-void tsx_log_end(tsx_solver *s, int ev, hipEvent_t a) {
-  TsxLog *L = s->log;
-  TsxRoctx &r = tsx_roctx();
-  L->count[ev] += 1;
-  hipEvent_t b = a ? tsx_log_event(L) : nullptr;
-  if (b && hipEventRecord(b, s->stream) == hipSuccess) {
-    L->pending.push_back({ev, a, b});
-    if (L->pending.size() > 256) tsx_log_retire(s, false);
-  }
-  if (r.pop) r.pop();
-}
-static void tsx_log_free(tsx_solver *s) {
-  if (!s->log) return;
-  tsx_log_retire(s, true);
-  for (hipEvent_t e : s->log->pool) (void)hipEventDestroy(e);
-  delete s->log;
-  s->log = nullptr;
-}
-extern "C" int tsx_log_enable(tsx_solver *s, int on) {
-  ARGCHK(s, "tsx_log_enable: null");
-  HIPCHK(hipSetDevice(s->device));
-  if (on && !s->log) s->log = new TsxLog();
-  if (!on) tsx_log_free(s);
-  return TSX_OK;
-}
-extern "C" int tsx_log_get(tsx_solver *s, int32_t *nevents, const char **names, int64_t *counts, double *ms) {
-  ARGCHK(s && nevents, "tsx_log_get: null");
-  *nevents = TSX_EV_COUNT;
-  if (!s->log) {
-    tsx_set_error("tsx_log_get: log events are off (tsx_log_enable, or TSX_LOG=1 at tsx_create)");
-    return TSX_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  tsx_log_retire(s, true);
-  int n = 0;
-  for (int q = 0; q < TSX_EV_TOTAL; ++q) {
-    if (q >= TSX_EV_COUNT && s->log->count[q] == 0) continue;  // the 1-D solvers' events: listed once they have fired
-    if (names) names[n] = kLogNames[q];
-    if (counts) counts[n] = s->log->count[q];
-    if (ms) ms[n] = s->log->ms[q];
-    ++n;
-  }
-  *nevents = n;
-  return TSX_OK;
-}
-
-// ---- diagnostics: a translation unit's code as it sits in device memory (TSX_CODE_PROBE, tsx_host.hpp).  unit 0..7 = api, spmv310,
-// spmv816, pc, pcs, pcsflow, dedup, peer (the order of the code objects in libtsx.so is the link order, scripts/code_verify.py finds
-// them by the probe's symbol).  Copies nwords 32-bit words from (probe's pc + delta) to host_out and returns the pc in *pc_out; with
-// nwords = 0 only the pc.  The caller is responsible for the range lying inside the loaded code object.
-extern "C" int tsx_debug_code_read(int device, int unit, long long delta, long long nwords, void *host_out, unsigned long long *pc_out) {
-  ARGCHK(unit >= 0 && unit < 8 && nwords >= 0 && pc_out && (nwords == 0 || host_out), "tsx_debug_code_read: bad arguments");
-  if (device >= 0) HIPCHK(hipSetDevice(device));
-  typedef int (*probe_fn)(long long, long long, unsigned *, unsigned long long *, hipStream_t);
-  static const probe_fn probes[8] = {tsx_code_probe_api, tsx_code_probe_spmv310, tsx_code_probe_spmv816, tsx_code_probe_pc,
-                                     tsx_code_probe_pcs, tsx_code_probe_pcsflow, tsx_code_probe_dedup, tsx_code_probe_peer};
-  TsxDevTmp out, pc;
-  HIPCHK(out.alloc(sizeof(unsigned) * (size_t)(nwords > 0 ? nwords : 1)));
-  HIPCHK(pc.alloc(sizeof(unsigned long long)));
-  if (probes[unit](delta, nwords, out.as<unsigned>(), pc.as<unsigned long long>(), nullptr)) {
-    tsx_set_error("tsx_debug_code_read: launch failed");
-    return TSX_ERR_HIP;
-  }
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(pc_out, pc.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (nwords > 0) HIPCHK(hipMemcpy(host_out, out.p, sizeof(unsigned) * (size_t)nwords, hipMemcpyDeviceToHost));
-  return TSX_OK;
-}
-
-#include "tsx_pipeline_api.inc"
-#include "tsx_seam_api.inc"
 
 TSX_CODE_PROBE(api)  // tsx_host.hpp: this unit's code object as it sits in device memory (diagnostics)

@@ -453,7 +453,7 @@ static int dd_build(tsx_solver *s, bool near, bool *pays) {
   return TSX_OK;
 }
 
-// TSX_DEBUG_CHECKS (tests only, tsx_pipeline_api.inc): directly behind tsx_k_dd_index the representatives are read back.  The rare wrong
+// TSX_DEBUG_CHECKS (tests only, tsx_pipeline.hip): directly behind tsx_k_dd_index the representatives are read back.  The rare wrong
 // result of rounds 4-5 had ent_cell = {0, 0, 0, 0} on rank 0 while both indices written by the SAME launch were right: this says whether
 // the stores never arrived (zero right here) or were wiped later, and a second launch of the same kernel into the same buffer says
 // whether the loss is transient or a property of the process (e.g. of its copy of the kernel's code).

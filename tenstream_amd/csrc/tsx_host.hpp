@@ -1,4 +1,4 @@
-// tsx_host.hpp -- host-side helpers shared by the translation units of libtsx (tsx_api.hip, tsx_spmv_*.hip, tsx_pc.hip)
+// tsx_host.hpp -- host-side helpers shared by the translation units of libtsx
 #pragma once
 #include <stdlib.h>
 
@@ -103,7 +103,7 @@ struct TsxDevTmp {
 // ---- code probe (diagnostics): every translation unit is a code object of its own inside libtsx.so (no -fgpu-rdc); the probe
 // kernel of a unit reports its own program counter and copies `nwords` 32-bit words from pc + delta to `out`, so that a host tool
 // that knows the unit's ELF (scripts/code_verify.py: symbol table + the s_getpc_b64 inside the probe) can compare the code AS IT
-// SITS IN DEVICE MEMORY with the bytes in the file (tsx_debug_code_read, tsx_api.hip).  Round 6: the hunt for the rare wrong
+// SITS IN DEVICE MEMORY with the bytes in the file (tsx_debug_code_read, tsx_diag.hip).  Round 6: the hunt for the rare wrong
 // result of the four-process pipeline test asked whether a process can run a damaged copy of a kernel.
 #define TSX_CODE_PROBE(TU)                                                                                                     \
   extern "C" __global__ void tsx_k_code_probe_##TU(long long delta, long long nwords, unsigned *out, unsigned long long *pc_out) { \
@@ -120,13 +120,32 @@ struct TsxDevTmp {
   }
 #define TSX_CODE_PROBE_DECL(TU) int tsx_code_probe_##TU(long long, long long, unsigned *, unsigned long long *, hipStream_t);
 TSX_CODE_PROBE_DECL(api) TSX_CODE_PROBE_DECL(spmv310) TSX_CODE_PROBE_DECL(spmv816) TSX_CODE_PROBE_DECL(pc) TSX_CODE_PROBE_DECL(pcs)
-TSX_CODE_PROBE_DECL(pcsflow) TSX_CODE_PROBE_DECL(dedup) TSX_CODE_PROBE_DECL(peer)
+TSX_CODE_PROBE_DECL(pcsflow) TSX_CODE_PROBE_DECL(dedup) TSX_CODE_PROBE_DECL(peer) TSX_CODE_PROBE_DECL(coeff) TSX_CODE_PROBE_DECL(pipeline)
+TSX_CODE_PROBE_DECL(diag)
 
 // ---- cross-unit entry points --------------------------------------------------------------------
 // face exchange on stream st (RCCL / host-staged callbacks / self copies), tsx_api.hip
 int tsx_face_exchange(tsx_solver *s, hipStream_t st);
 int tsx_face_exchange_elems(tsx_solver *s, hipStream_t st, size_t elem_bytes);  // the diffuse halo with elements of that size
 int tsx_face_exchange_bufs(tsx_solver *s, hipStream_t st, double *const send[4], double *const recv[4], size_t cx, size_t cy);
+// tsx_api.hip: sum over the ranks of n (<= TSX_NSLOTS) host doubles / of one double on the device (every use of RCCL lives there)
+int tsx_allreduce_host(tsx_solver *s, double *v, int n);
+int tsx_allreduce_dev1(tsx_solver *s, double *d);
+// tsx_api.hip: an internal vector (with its halo) out to the reference's layout; the solver's settings for a solve; the Krylov loop
+// on s->vb / s->vx with the retry of a failed solve; the result of the loop that has just ended
+int tsx_export_vec(tsx_solver *s, const double *v, double *ref_dev);
+int tsx_prepare_ksp(tsx_solver *s, const tsx_ksp_opts *opts, tsx_ksp_opts *o);
+int tsx_krylov_run_with_retry(tsx_solver *s, tsx_ksp_opts *o);
+int tsx_fill_result(tsx_solver *s, tsx_ksp_result *res);
+// tsx_coeff.hip: storage of the dense planes; every cell's diffuse block from the LUT (buildings: patched before anything is shared);
+// a (k,i,j) cell field into cell order; the axes of the LUT_3_10 / LUT_8_16 tables
+int tsx_ensure_coef_storage(tsx_solver *s, int out_bytes);
+int tsx_lut_diffuse_launch(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx, bool buildings = false);
+int tsx_keep_cellfield(tsx_solver *s, double **dst, const double *src, int where);
+extern const float tsx_preset_tau31[31], tsx_preset_w020[20], tsx_preset_aspect23[23], tsx_preset_g6[6];
+// tsx_pipeline.hip: the stored solutions of a handle; tsx_diag.hip: its log events (both for tsx_destroy)
+void tsx_slots_free(tsx_solver *s);
+void tsx_log_free(tsx_solver *s);
 
 // operator apply: one translation unit per stream configuration (tsx_spmv_3_10.hip, tsx_spmv_8_16.hip).
 // combo = (fused dots, type of x, type of w): the variants the Krylov loop uses
@@ -168,7 +187,7 @@ int tsx_pc_ensure_buffers(tsx_solver *s);
 int tsx_pc_ensure_half(tsx_solver *s);
 int tsx_pc_narrow(tsx_solver *s, const double *a);
 int tsx_pc_widen(tsx_solver *s, const float *a, double *o);  // o = (double) a over the N unknowns
-int tsx_cell_samples(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx);  // tsx_api.hip
+int tsx_cell_samples(tsx_solver *s, const double *kabs, const double *ksca, const double *g, const double *dz, double dx);  // tsx_coeff.hip
 // shared storage of bit-identical blocks (tsx_dedup.hip)
 int tsx_dedup_ensure(tsx_solver *s);
 struct TsxLutDev;
@@ -177,7 +196,6 @@ int tsx_coef_ensure_dense(tsx_solver *s);  // dense per-cell planes, expanded fr
 // the red-black preconditioner of 3_10 as a segmented scan over the levels (tsx_pcs.hip); packed layout "S16" in s->coef_h
 bool tsx_pcs_eligible(const tsx_solver *s);
 int tsx_pc_global_agree(tsx_solver *s);       // tsx_pcs.hip: collective, see there
-int tsx_allreduce_host(tsx_solver *s, double *v, int n);  // tsx_api.hip (tsx_pipeline_api.inc)
 int tsx_pcs_pack(tsx_solver *s);
 int tsx_pcs_apply(tsx_solver *s, float *z, const int *done);
 int tsx_pcs_pass(tsx_solver *s, int pass, int mode, float *zfin, const int *done, int rq, int part = 0);

@@ -121,7 +121,7 @@ struct tsx_solver {
   // operator
   void *coef;          // planes, float or double
   int coef_bytes;      // 4 or 8
-  void *coef_h;        // packed fp16 copy of the blocks for the preconditioner (tsx_k_pack_p16; built in prepare_ksp)
+  void *coef_h;        // packed fp16 copy of the blocks for the preconditioner (tsx_k_pack_p16; built in tsx_prepare_ksp)
   bool coef_h_valid, pc_half;
   bool coef_h_dd;      // ... with groups 1..7 stored per distinct block (tsx_dedup.hip)
   bool coef_h_scan;    // the packed copy is in the scan kernels' layout "S16" (tsx_kernels_pcs.hpp; always colour-split)

@@ -169,7 +169,7 @@ static bool pcs_peer_inkernel(const tsx_solver *s) {
 // with the four neighbours, so one rank deciding differently (an odd local extent from an uneven split such as
 // xs = (xi * Nx) / nxp with Nx = 7, or zebra rows after the local red-black fallback) would leave its neighbours' messages
 // unmatched or paired with the operator's halo messages.  pcs_halo_local is this rank's vote, tsx_pc_global_agree
-// (called from prepare_ksp / tsx_diff_pc_apply, collective) the all-reduce.  All extents even on all ranks also means
+// (called from tsx_prepare_ksp / tsx_diff_pc_apply, collective) the all-reduce.  All extents even on all ranks also means
 // xs and ys are even everywhere (sums of even extents), so the local colour (i + j) & 1 is the global colour.
 static bool pcs_halo_local(const tsx_solver *s) {
   const TsxGeo &g = s->geo;

@@ -5,7 +5,8 @@
 // Direct streams are stored on the column they sit on (reference ownership), one plane per stream:
 //     E[s * Ncl + (k * ym + j) * xm + i],  k = 0..Nz (levels),  Ncl = (Nz+1) * ncol
 #pragma once
-#include "tsx_kernels.hpp"
+#include "tsx_dev.hpp"
+#include "tsx_lut_dev.hpp"
 #include "tsx_kernels_1d.hpp"
 
 struct TsxSun {

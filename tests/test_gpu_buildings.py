@@ -12,7 +12,7 @@ flux tolerance.
 Scenes: the reference's own 6 x 6 x 3 known-answer scene with one full box at glob_box (i, j, k) = (3, 3, 2)
 (tests/test_buildings/test_buildings.F90:157-158); a 6 x 6 x 4 scene with a roof only, a two-cell wall and a RIGHT and a FRONT face
 on the last column / row (their dofs wrap); and 4 x 4 x 3 with default tolerances for the scan preconditioner: the rule in
-prepare_ksp (tsx_api.hip) wants fp32 directions (rtol >= 1e-7), xm even and >= 2, ym even on a periodic rank and Nz <= 256 --
+tsx_prepare_ksp (tsx_api.hip) wants fp32 directions (rtol >= 1e-7), xm even and >= 2, ym even on a periodic rank and Nz <= 256 --
 2 x 2 x 1 satisfies it, but a building there is its own neighbour on every side; 4 x 4 x 3 is the smallest even grid on which a full
 box has a free cell on each of its six sides."""
 import ctypes
